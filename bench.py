@@ -19,9 +19,20 @@ staged to HBM, multiplied by W (one fused MFMA GEMM+ReLU kernel per chunk)
 and the float32[512] output column is written back to page-locked host
 memory (PCIe traffic both ways is inside the timed region).
 
-`--mode device` additionally times the same pass on a DataFrame cached in
-HBM (`cache_on_device()`, outputs stay in HBM) and reports it as an extra
-field; the headline `value` is always the host-resident pass.
+A plain run does only what the headline figure needs: set up, warm up, time
+the steps, print the JSON line. `--full` adds everything else the benchmark
+measures or checks: the spot check of the last step's output against an fp64
+reference (`max_abs_err`), and (with `--mode device` or `both`, the default)
+the same pass timed on a DataFrame cached in HBM (`cache_on_device()`,
+outputs stay in HBM), reported as extra fields. The headline `value` is
+always the host-resident pass.
+
+`--dump-outputs DIR` writes what the last timed step returned: a fixed,
+seeded sample of the float32[512] output rows as `DIR/y.npy` (float32) and
+the global row numbers of the sample as `DIR/y_rows.npy` (float64). With
+more than one rank each rank writes the sampled rows it owns
+(`y.rank<r>.npy`, `y_rows.rank<r>.npy`). The inputs are seeded, so two runs
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -48,7 +59,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=TOTAL_ROWS)
     ap.add_argument("--parts-per-gpu", type=int, default=4)
-    ap.add_argument("--mode", choices=["host", "device", "both"], default="both")
+    ap.add_argument("--mode", choices=["host", "device", "both"], default="both",
+                    help="with --full: also time the HBM-resident pass (device, both)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the output spot check and the HBM-resident pass (see --mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's output rows to DIR/*.npy")
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu: rehearse the launcher/collectives on the host (gloo), e.g. in CPU tests")
     return ap.parse_args()
@@ -82,6 +98,30 @@ def _chosen_tiles():
             out.append({"M": key[0], "N": key[1], "K": key[2], "tile": tile, "dims": f"{bm}x{bn}",
                         "core": "g2" if core == 2 else "round4", "default": dflt[0] if dflt else None})
     return out
+
+
+DUMP_ROWS = 16384  # sampled output rows: 16384 x 512 float32 = 32 MiB
+
+
+def dump_outputs(out_dir, res, nparts, total_rows, rank, world):
+    """Write a fixed, seeded sample of the last step's output rows. `res` maps
+    this rank's partition ids to their output blocks; partition p holds the
+    global rows [p * total // nparts, (p + 1) * total // nparts)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = min(DUMP_ROWS, total_rows)
+    rows = np.sort(np.random.default_rng(20240607).choice(total_rows, size=n, replace=False))
+    got_rows, got = [], []
+    for p in sorted(res):
+        a, b = (p * total_rows) // nparts, ((p + 1) * total_rows) // nparts
+        sel = rows[(rows >= a) & (rows < b)]
+        ycol = res[p].columns["y"]
+        got_rows.append(sel)
+        got.append(ycol[torch.as_tensor(sel - a, dtype=torch.long)].cpu().numpy().astype(np.float32))
+    suffix = "" if world == 1 else f".rank{rank}"
+    np.save(os.path.join(out_dir, f"y{suffix}.npy"),
+            np.concatenate(got) if got else np.zeros((0, DIM), np.float32))
+    np.save(os.path.join(out_dir, f"y_rows{suffix}.npy"),
+            (np.concatenate(got_rows) if got_rows else np.zeros(0)).astype(np.float64))
 
 
 def main():
@@ -188,16 +228,20 @@ def rank_main(args):
 
     results, own = {}, {}
     dt, own["host"], res = timed(step_host, args.steps, args.warmup)
-    # correctness spot check on a few rows of the first local partition
-    pid = min(res)
-    xin = blocks[pid].columns["x"][:64].double()
-    ref = torch.clamp_min(xin @ torch.as_tensor(w).double(), 0)
-    err = (res[pid].columns["y"][:64].double() - ref).abs().max().item()
-    assert err < 1e-3, f"wrong result: max abs err {err}"
     results["host"] = dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, nparts, args.rows, rank, world)
+    err = None
+    if args.full:
+        # correctness spot check on a few rows of the first local partition
+        pid = min(res)
+        xin = blocks[pid].columns["x"][:64].double()
+        ref = torch.clamp_min(xin @ torch.as_tensor(w).double(), 0)
+        err = (res[pid].columns["y"][:64].double() - ref).abs().max().item()
+        assert err < 1e-3, f"wrong result: max abs err {err}"
 
     dev_rows_per_s = None
-    if args.mode in ("device", "both") and use_gpu:
+    if args.full and args.mode in ("device", "both") and use_gpu:
         base_dev = base.cache_on_device(dev)
 
         def step_dev():
@@ -212,16 +256,19 @@ def rank_main(args):
     # one diagnostic line per rank on stderr (the driver's 8-GPU run is
     # diagnosable from its log): placement, backend, page-locked memory, own time
     pool = _C.pinned_pool_stats() if use_gpu else {}
-    print(json.dumps({"bench_rank": rank, "local_rank": dist.local_rank(), "world_size": world,
-                      "backend": backend, "device": str(dev),
-                      "numa_cpus": (f"{min(numa_cpus)}-{max(numa_cpus)}" if numa_cpus else None),
-                      "numa_cpu_count": len(numa_cpus),
-                      "pinned_live_bytes": pool.get("live"), "pinned_peak_bytes": pool.get("peak"),
-                      "pinned_cap_bytes": pool.get("limit"),
-                      "own_ms_per_step": own["host"] / args.steps * 1e3,
-                      "own_device_ms_per_step": (own["device"] / args.steps * 1e3) if "device" in own else None,
-                      "rows": sum(b.nrows for b in blocks.values()), "partitions": sorted(blocks)}),
-          file=sys.stderr, flush=True)
+    line = json.dumps({"bench_rank": rank, "local_rank": dist.local_rank(), "world_size": world,
+                       "backend": backend, "device": str(dev),
+                       "numa_cpus": (f"{min(numa_cpus)}-{max(numa_cpus)}" if numa_cpus else None),
+                       "numa_cpu_count": len(numa_cpus),
+                       "pinned_live_bytes": pool.get("live"), "pinned_peak_bytes": pool.get("peak"),
+                       "pinned_cap_bytes": pool.get("limit"),
+                       "own_ms_per_step": own["host"] / args.steps * 1e3,
+                       "own_device_ms_per_step": (own["device"] / args.steps * 1e3) if "device" in own else None,
+                       "rows": sum(b.nrows for b in blocks.values()), "partitions": sorted(blocks)})
+    # the ranks share one stderr: text and newline go out in one write, so two
+    # ranks' lines cannot run into each other
+    sys.stderr.flush()
+    os.write(sys.stderr.fileno(), (line + "\n").encode())
     if rank == 0:
         out = {
             "metric": "rows/sec map_blocks MatMul on 10M-row DF at 1/2/4/8 MI355X",
@@ -230,6 +277,7 @@ def rank_main(args):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms,
             "higher_is_better": True,
             "scaling": "strong",

@@ -65,7 +65,7 @@ for s in ${STEPS:-tests}; do
     cfg_add) run cfg_add 600 python bench/configs.py add ;;
     cfg_plumbing) run cfg_plumbing 300 python bench/configs.py plumbing ;;
     cfg_reduce) run cfg_reduce 900 python bench/configs.py reduce ;;
-    bench) run bench 900 python bench.py --steps 5 --warmup 2 ;;
+    bench) run bench 900 python bench.py --full --steps 5 --warmup 2 ;;
     smi) run smi_$(date +%H%M%S) 60 rocm-smi --showclocks --showpower --showtemp --showuse ;;
     rehearse2) TFA_DIST_BACKEND=gloo run rehearse2 600 python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 scripts/multirank_rehearsal.py ;;
     incep_sweep2) for b in 2048 4096 8192; do run incep_b$b 600 python bench/configs.py inception --source device --rows 16384 --batch $b --steps 2 --warmup 1; done ;;
@@ -115,7 +115,7 @@ for s in ${STEPS:-tests}; do
       run trace_vgg_window 120 python scripts/trace_window.py gpurun_out/trace_vgg --out gpurun_out/trace_vgg_step.md --title "VGG-16 JPEG scoring (read_image), 4096 images: the steady-state pass" ;;
     # ---- presets (the one-off round-4/5 step lists, folded in)
     final) STEPS=smoke bash scripts/gpu_check.sh && run tests 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread &&
-      run bench 900 python bench.py --steps 5 --warmup 2 &&
+      run bench 900 python bench.py --full --steps 5 --warmup 2 &&
       run incep_dev 900 python bench/configs.py inception --source device --rows 16384 --steps 2 --warmup 1 ;;
     prec) run prec 300 python -u -m pytest tests/test_gpu_precision.py tests/test_gpu_g2.py -x -q --timeout 300 --timeout-method thread ;;
     tile_ab) run tile_ab 900 bash scripts/tile_ab.sh ;;                    # SHAPES=<file> TILES="auto 16 28 ..."

@@ -49,7 +49,7 @@ def main():
         os.remove(tmp)
     # no defaults while measuring: every shape is tuned from scratch
     env = dict(os.environ, TFA_GEMM_TUNE_DUMP=tmp, TFA_GEMM_DEFAULTS="0")
-    runs = [[sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--mode", "device"],
+    runs = [[sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--full", "--mode", "device"],
             [sys.executable, "bench/configs.py", "inception", "--source", "device", "--rows", "4096", "--steps", "1",
              "--warmup", "1"]]
     for cmd in runs:

@@ -216,8 +216,13 @@ def _check_results(tmp_path, world, device, shm=False):
         assert o["pq_x"] == xs and o["pq_parts"] == o["local_parts"]
 
 
-def test_parse_cpulist_and_bind_numa_noop_without_gpu():
+def test_parse_cpulist_and_bind_numa_noop_without_gpu(monkeypatch):
     from tensorframes_amd.parallel import dist as D
     assert D._parse_cpulist("0-3,8,10-11\n") == [0, 1, 2, 3, 8, 10, 11]
     assert D._parse_cpulist("") == []
+    # the premise holds on a GPU machine too (where a real bind would also
+    # narrow the CPU set of the test process for the rest of the run)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    before = os.sched_getaffinity(0)
     assert D.bind_numa() == []  # no GPU here: nothing to bind
+    assert os.sched_getaffinity(0) == before

@@ -13,7 +13,7 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run_bench(n, rows=4096, extra=()):
+def _run_bench(n, rows=4096, extra=("--full",)):  # --full: the output spot check (max_abs_err)
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
@@ -46,6 +46,33 @@ def test_bench_spawns_n_ranks(n):
     assert sorted(p for d in ranks for p in d["partitions"]) == list(range(4 * n))
     assert all(p % n == d["bench_rank"] for d in ranks for p in d["partitions"])
     assert sum(d["rows"] for d in ranks) == 4096
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the run times the headline only (no spot check, no
+    device-resident pass); --dump-outputs writes the sampled rows of the last
+    timed step, identical from run to run and equal to relu(x @ W)."""
+    import numpy as np
+    import torch
+    rows, parts, dim = 1000, 4, 512
+    outs = []
+    for d in ("a", "b"):
+        out = _run_bench(1, rows=rows, extra=("--dump-outputs", str(tmp_path / d)))
+        assert out["full"] is False and out["steps"] == 2 and out["ms_per_step"] > 0
+        assert out["max_abs_err"] is None and out["device_resident_rows_per_sec"] is None
+        assert sorted(os.listdir(tmp_path / d)) == ["y.npy", "y_rows.npy"]
+        outs.append((np.load(tmp_path / d / "y.npy"), np.load(tmp_path / d / "y_rows.npy")))
+    (y, r), (y2, r2) = outs
+    assert y.dtype == np.float32 and y.shape == (rows, dim) and r.dtype == np.float64
+    np.testing.assert_array_equal(r, np.arange(rows))  # fewer rows than the sample size: all of them
+    np.testing.assert_array_equal(y, y2)
+    np.testing.assert_array_equal(r, r2)
+    # the benchmark's seeded inputs, rebuilt here
+    x = torch.cat([torch.randn(((p + 1) * rows // parts - p * rows // parts, dim),
+                               generator=torch.Generator().manual_seed(1000 + p)) for p in range(parts)])
+    w = (torch.randn((dim, dim), generator=torch.Generator().manual_seed(7)) / np.sqrt(dim)).float()
+    want = torch.clamp_min(x.double() @ w.double(), 0).numpy()
+    assert np.abs(y - want).max() < 1e-3
 
 
 def test_launcher_propagates_failure(tmp_path):

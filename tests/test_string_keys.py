@@ -107,6 +107,9 @@ def _worker(rank, world, port, outdir):
     from tensorframes_amd import tf
     from tensorframes_amd.parallel import dist
     from tensorframes_amd.utils.logging import metrics
+    # this module imported the package (and read TFA_DEVICE) while the child
+    # unpickled _worker, before the line above set it: say it again
+    tfs.set_config(device="cpu")
     assert dist.init(backend="gloo")
     rng = np.random.default_rng(7)
     keys = np.array([f"user-{i % 97:03d}" * (1 + i % 3) for i in range(6000)])
