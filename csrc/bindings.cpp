@@ -637,6 +637,69 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     c10::hip::HIPGuard guard(rec.device().index());
     k::unpack_rows(pc, rec.contiguous().data_ptr(), n, R, c10::hip::getCurrentHIPStream(rec.device().index()).stream());
   }, "records [n, R] -> the preallocated device columns (same layout as pack_rows)");
+  // DataFrame.filter on device-resident partitions (kernels/compact.hip)
+  m.def("compact_tile_rows", [] { return k::compact_tile_rows(); }, "rows per tile of the row-compaction kernels");
+  m.def("compact_rows", [](const at::Tensor& mask0, const std::vector<at::Tensor>& cols, bool want_index) {
+    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("compact_rows: 1..", k::kMaxPackCols, " columns per call, got ", cols.size()));
+    if (mask0.scalar_type() != at::kBool && mask0.scalar_type() != at::kByte)
+      throw py::type_error(str_cat("compact_rows: the mask must be bool or uint8, got ", c10::toString(mask0.scalar_type())));
+    if (!mask0.is_cuda()) throw py::value_error("compact_rows: the mask must be a device tensor");
+    if (cols[0].dim() < 1) throw py::value_error("compact_rows: columns need a row dimension");
+    const int64_t n = cols[0].size(0);
+    if (mask0.dim() != 1 || mask0.size(0) != n)
+      throw py::value_error(str_cat("compact_rows: the mask must hold one entry per row ([", n, "]), got ",
+                                    mask0.dim(), "-D with ", mask0.numel(), " entries"));
+    std::vector<at::Tensor> src;
+    for (size_t c = 0; c < cols.size(); ++c) {
+      const at::Tensor& t = cols[c];
+      if (!t.is_cuda() || t.device() != mask0.device())
+        throw py::value_error(str_cat("compact_rows: column ", c, " is not on the mask's device"));
+      if (t.dim() < 1 || t.size(0) != n)
+        throw py::value_error(str_cat("compact_rows: column ", c, " has ", t.dim() < 1 ? 0 : t.size(0),
+                                      " rows, column 0 has ", n));
+      src.push_back(t.contiguous());
+    }
+    c10::hip::HIPGuard guard(mask0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(mask0.device().index()).stream();
+    at::Tensor mask = mask0.contiguous();
+    const uint8_t* mp = static_cast<const uint8_t*>(mask.data_ptr());
+    int64_t total = 0;
+    at::Tensor ws;
+    if (n > 0) {
+      const size_t wsb = k::compact_workspace_bytes(n);
+      // (int64 elements: the workspace starts with 64-bit offsets)
+      ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, mask.options().dtype(at::kLong));
+      py::gil_scoped_release nogil;
+      total = k::compact_plan(mp, n, ws.data_ptr(), ws.numel() * 8, s);
+    }
+    k::PackCols ps, pd;
+    ps.n = pd.n = static_cast<int>(src.size());
+    std::vector<at::Tensor> outs;
+    for (size_t c = 0; c < src.size(); ++c) {
+      std::vector<int64_t> shape = src[c].sizes().vec();
+      int64_t cell = 1;
+      for (size_t d = 1; d < shape.size(); ++d) cell *= shape[d];
+      shape[0] = total;
+      at::Tensor o = pool_empty(shape, src[c].options());
+      ps.row_bytes[c] = pd.row_bytes[c] = cell * static_cast<int64_t>(src[c].element_size());
+      ps.off[c] = pd.off[c] = 0;
+      ps.ptr[c] = src[c].data_ptr();
+      pd.ptr[c] = o.data_ptr();
+      outs.push_back(o);
+    }
+    py::object index = py::none();
+    int64_t* ip = nullptr;
+    if (want_index) {
+      at::Tensor it = pool_empty({total}, mask.options().dtype(at::kLong));
+      ip = it.data_ptr<int64_t>();
+      index = py::cast(it);
+    }
+    if (n > 0 && total > 0) k::compact_gather(ps, pd, mp, n, total, ws.data_ptr(), ip, s);
+    return py::make_tuple(outs, total, index);
+  }, py::arg("mask"), py::arg("cols"), py::arg("want_index") = false,
+     "rows of the device columns whose mask entry is non-zero, in order -> (compacted columns, kept count, "
+     "int64 indices of the kept rows or None); one stream synchronisation reads the count");
   // native JPEG decode into one ragged (pinned) buffer (runtime/jpeg_decode.cpp)
   struct PyJpegBatch {
     std::vector<py::buffer_info> views;  // keep the cells' buffers exported while decoding

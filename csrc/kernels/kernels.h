@@ -150,6 +150,21 @@ size_t partition_workspace_bytes(int64_t n);
 void partition_rows(const int64_t* dest, int64_t n, int64_t world, int64_t* perm, int64_t* counts, void* workspace,
                     size_t workspace_size, hipStream_t s);
 
+// ------------------------------------------------------------ row compaction (compact.hip)
+// Stable compaction of whole rows by a byte mask (non-zero keeps the row):
+// compact_plan counts the kept rows per tile of compact_tile_rows() rows,
+// scans the tile counts into the workspace and returns the total
+// (synchronises the stream once to read it, like factorize); compact_gather
+// then copies the kept rows of every column src.ptr[c] [n, src.row_bytes[c]]
+// into dst.ptr[c] [total, row_bytes[c]] (the `off` fields are ignored) and,
+// when `index` is not null, writes the kept row indices [total]. The mask
+// must not change between the two calls.
+int compact_tile_rows();
+size_t compact_workspace_bytes(int64_t n);
+int64_t compact_plan(const uint8_t* mask, int64_t n, void* workspace, size_t workspace_size, hipStream_t s);
+void compact_gather(const PackCols& src, const PackCols& dst, const uint8_t* mask, int64_t n, int64_t total,
+                    const void* workspace, int64_t* index, hipStream_t s);
+
 // ------------------------------------------------------------ data movement
 // dst[idx] = src[idx] over `dims`, both operands addressed by element strides
 // (src strides may be 0 or negative; pointers already include the offsets).

@@ -28,6 +28,7 @@ from ..parallel import dist
 from ..utils import dtypes as D
 from .block import (Block, ObjectColumn, RaggedColumn, StringColumn, build_column, build_rows, column_values, concat_blocks,
                     is_dense)
+from .column import Column, compile_expressions
 from .column_info import ColumnInformation, DataFrameInfo, explain_schema
 from .types import (ArrayType, BinaryType, BooleanType, DataType, DoubleType, FloatType, IntegerType,
                     LongType, NumericType, Row, StringType, StructField, StructType, scalar_type_of)
@@ -184,6 +185,34 @@ class DataFrame:
 
     def printSchema(self):  # noqa: N802
         print(explain_schema(self._schema), end="")
+
+    # -- columns
+    def __getattr__(self, name: str) -> Column:
+        # only reached when the ordinary lookup fails: answers for schema names
+        # alone, and not before `_schema` exists (copy / pickle probe a blank
+        # instance for dunder methods; asking `self._schema` here would recurse)
+        schema = self.__dict__.get("_schema")
+        if schema is None or name.startswith("__") or name not in schema:
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}'")
+        return Column._ref(name, schema[name])
+
+    def __getitem__(self, item):
+        """`df["x"]` -> Column; `df[["a", "b"]]` -> select; `df[predicate]` -> filter."""
+        if isinstance(item, str):
+            if item not in self._schema:
+                raise ValueError(f"Column {item} not found in {self.columns}")
+            return Column._ref(item, self._schema[item])
+        if isinstance(item, Column):
+            return self.filter(item)
+        if isinstance(item, (list, tuple)):
+            return self.select(*item)
+        if isinstance(item, numbers.Integral) and not isinstance(item, bool):
+            if not -len(self._schema.fields) <= item < len(self._schema.fields):
+                raise IndexError(f"column index {item} out of range for {len(self._schema.fields)} columns")
+            f = self._schema.fields[item]
+            return Column._ref(f.name, f)
+        raise TypeError(f"DataFrame[...] takes a column name, a list of columns or a boolean Column, "
+                        f"got {type(item).__name__}")
 
     def explain_tensors(self) -> str:
         """`DataFrame[double[?,2], ...]` (reference: src/main/scala/org/tensorframes/DataFrameInfo.scala:10-17)."""
@@ -359,13 +388,126 @@ class DataFrame:
 
     # -- transformations
     def select(self, *cols) -> "DataFrame":
+        """Columns by name or `Column` expressions, mixed. A plain reference
+        (aliased or not) is zero-copy: the same tensor under the new name, the
+        field copied with all of its metadata. Computed expressions of one
+        select run as ONE map_blocks over a generated graph."""
         names = [c for cs in cols for c in (cs if isinstance(cs, (list, tuple)) else [cs])]
+        if any(isinstance(n, Column) for n in names):
+            return self._select_columns(names)
         for n in names:
             if n not in self._schema:
                 raise ValueError(f"Column {n} not found in {self.columns}")
         schema = StructType([self._schema[n] for n in names])
         return DataFrame(schema, _Derived(self, lambda bs: {p: b.select(names) for p, b in bs.items()}),
                          self._nparts)
+
+    def _project(self, pairs: Sequence[tuple]) -> "DataFrame":
+        """Zero-copy projection: [(column here, name there)]."""
+        pairs = list(pairs)
+        schema = StructType([self._schema[src] if src == dst else self._schema[src].copy(name=dst)
+                             for src, dst in pairs])
+
+        def fn(bs):
+            return {p: Block(b.nrows, {dst: b.columns[src] for src, dst in pairs}) for p, b in bs.items()}
+        return DataFrame(schema, _Derived(self, fn), self._nparts)
+
+    def _select_columns(self, items: Sequence[Any]) -> "DataFrame":
+        from .. import core
+        outs: List[tuple] = []  # (output name, source column or None, expression)
+        for it in items:
+            if isinstance(it, str):
+                it = Column._ref(it)
+            elif not isinstance(it, Column):
+                raise TypeError(f"select: a column name or a Column is expected, got {type(it).__name__}")
+            if it.is_reference:
+                src = it._expr[1]
+                if src not in self._schema:
+                    raise ValueError(f"Column {src} not found in {self.columns}")
+                outs.append((it.output_name, src, None))
+            else:
+                outs.append((it.output_name, None, it._expr))
+        seen = set()
+        for name, _, _ in outs:
+            if name in seen:
+                raise ValueError(f"select: duplicate output column name '{name}'; give one of them an .alias()")
+            seen.add(name)
+        base = self
+        computed = [(i, e) for i, (_, src, e) in enumerate(outs) if src is None]
+        tmp: Dict[int, str] = {}
+        if computed:
+            k = 0
+            for i, _ in computed:  # graph node names that meet no column name
+                while f"tfa_expr_{k}" in self._schema:
+                    k += 1
+                tmp[i] = f"tfa_expr_{k}"
+                k += 1
+            fetches, feed, infos = compile_expressions(self, [(tmp[i], e) for i, e in computed])
+            for (i, _), (dt, _) in zip(computed, infos):
+                if dt == D.DT_BOOL:
+                    raise core.InvalidTypeException(
+                        f"select: '{outs[i][0]}' is a boolean expression, which no column type can hold; "
+                        f"cast it, e.g. .cast(\"int\"), or use it in filter()")
+            base = core.map_blocks(fetches, self, feed_dict=feed)
+        return base._project([(tmp[i] if src is None else src, name) for i, (name, src, _) in enumerate(outs)])
+
+    def withColumn(self, name: str, expr: Column) -> "DataFrame":  # noqa: N802
+        """Appends column `name`; an existing column of that name is replaced
+        in place (keeps its position), as in Spark."""
+        if not isinstance(expr, Column):
+            raise TypeError(f"withColumn: a Column expression is expected, got {type(expr).__name__}")
+        new = expr.alias(name)
+        if name in self._schema:
+            return self._select_columns([new if c == name else c for c in self.columns])
+        return self._select_columns(list(self.columns) + [new])
+
+    with_column = withColumn
+
+    def toDF(self, *names) -> "DataFrame":  # noqa: N802
+        """The same columns under new names."""
+        names = [c for cs in names for c in (cs if isinstance(cs, (list, tuple)) else [cs])]
+        if len(names) != len(self.columns):
+            raise ValueError(f"toDF: {len(names)} names given for {len(self.columns)} columns "
+                             f"({', '.join(self.columns)})")
+        if len(set(names)) != len(names):
+            raise ValueError(f"toDF: duplicate column names in {names}")
+        return self._project(list(zip(self.columns, names)))
+
+    to_df = toDF
+
+    def filter(self, cond: Column) -> "DataFrame":  # noqa: A003
+        """Rows for which the boolean Column `cond` is true, in order; schema,
+        metadata and the number of partitions are unchanged (partition-local:
+        no collectives). Device-resident partitions are compacted on the
+        device by the row-compaction kernels (kernels/compact.hip); of a host
+        partition only the predicate's inputs travel to the GPU and only the
+        mask comes back."""
+        if not isinstance(cond, Column):
+            raise TypeError(f"filter: a boolean Column is expected (e.g. df.x > 3), got {type(cond).__name__}")
+        return _filter_frame(self, cond)
+
+    where = filter
+
+    def limit(self, n: int) -> "DataFrame":
+        """The first n rows in partition order; the number of partitions is
+        unchanged (later partitions become empty). Across ranks the rows per
+        partition are agreed with one host all-reduce."""
+        if not isinstance(n, numbers.Integral) or isinstance(n, bool) or n < 0:
+            raise ValueError(f"limit: a non-negative row count is expected, got {n!r}")
+        n = int(n)
+        nparts = self._nparts
+
+        def fn(bs):
+            from ..parallel import frame_comm
+            counts = frame_comm.partition_rows({p: b.nrows for p, b in bs.items()}, nparts)
+            res, before = {}, 0
+            for p in range(nparts):
+                if p in bs:
+                    keep = max(0, min(counts[p], n - before))
+                    res[p] = bs[p] if keep == counts[p] else bs[p].slice(0, keep)
+                before += counts[p]
+            return res
+        return DataFrame(self._schema, _Derived(self, fn, streamable=False), nparts)
 
     def drop(self, *names) -> "DataFrame":
         return self.select([n for n in self.columns if n not in names])
@@ -449,6 +591,133 @@ class DataFrame:
     def row(self, col_name: str, tf_name: Optional[str] = None):
         from .. import core
         return core.row(self, col_name, tf_name)
+
+
+# ------------------------------------------------------------------ filter
+_COMPACT_GROUP = 16  # columns per _C.compact_rows call (kernels.h kMaxPackCols)
+
+
+def _filter_frame(df: DataFrame, cond: Column) -> DataFrame:
+    """The lazy frame of `df.filter(cond)`. The predicate is validated here (one
+    bool per row, typed errors) and compiled to one program; every partition
+    then runs it directly -- not through map_blocks: the mask never becomes a
+    column -- and drops the rows the mask rejects."""
+    from .. import core, engine
+    from ..utils.logging import metrics
+    (fetch,), feed, ((dt, rank),) = compile_expressions(df, [("tfa_filter_mask", cond._expr)])
+    what = cond.output_name
+    if dt != D.DT_BOOL:
+        raise core.InvalidTypeException(
+            f"filter: the condition '{what}' is of type {D.dtype_name(dt)}, not boolean; compare it, "
+            f"e.g. ({what}) != 0")
+    if rank != 0:
+        raise core.InvalidDimensionException(
+            f"filter: the condition '{what}' yields a boolean cell of rank {rank} per row, not one value; "
+            f"reduce it with .all() or .any()")
+    spec = core._resolve([fetch])
+    summary = core.analyze_graph(spec)
+    out = summary[spec.fetch_names[0]]
+    if out.tf_dtype != D.DT_BOOL:
+        raise core.InvalidTypeException(f"filter: the condition '{what}' is of type {D.dtype_name(out.tf_dtype)}, "
+                                        f"not boolean")
+    if out.shape is not None and out.shape.num_dims != 1:
+        raise core.InvalidDimensionException(f"filter: the condition '{what}' has block shape {out.shape}, "
+                                             f"expected one value per row")
+    feed_names = [s.name for s in summary.values() if s.is_input]
+    feed_cols = [feed[n] for n in feed_names]
+    prog = engine.program_for_spec(spec, spec.fetch_refs, feed_names)
+    hints = {n: (summary[n].tf_dtype, list(core._col_info(df.schema[c]).shape.dims))
+             for n, c in zip(feed_names, feed_cols)}
+    separable = bool(feed_names) and bool(prog.row_separable(hints))
+
+    def mask_of(b: Block) -> torch.Tensor:
+        ins = core._dense_inputs(b, feed_cols, "filter")
+        if ins and all(t.is_cuda for t in ins) and len({t.device for t in ins}) == 1:
+            m = engine.run_program(prog, ins, ins[0].device)[0]  # stays on the device
+        elif not engine.gpu_available() or not ins:
+            m = engine.run_program(prog, ins, None)[0]
+            m = m.cpu() if m.is_cuda else m
+        elif separable and engine.worth_pipelining(ins):
+            # a large host partition: chunked H2D / compute / D2H; the mask is
+            # needed now, so the pipelined run is waited for here
+            with engine.deferred_pipelines() as handles:
+                m = engine.run_segments_pipelined(prog, [ins], [[((b.nrows,), torch.bool)]])[0][0]
+            engine.wait_pipelines(handles)
+            prog.release_pipeline()
+        else:
+            m = engine.run_block_host(prog, ins, False)[0]
+        if m.dim() != 1 or m.shape[0] != b.nrows:
+            raise core.InvalidDimensionException(
+                f"filter: the condition '{what}' produced shape {tuple(m.shape)} for a block of {b.nrows} rows")
+        return m if m.dtype == torch.bool else m != 0
+
+    def compute(blocks: Dict[int, Block]) -> Dict[int, Block]:
+        res: Dict[int, Block] = {}
+        rows_in = kept = 0
+        rng = torch.cuda.is_initialized()
+        if rng:
+            torch.cuda.nvtx.range_push("tfa.filter")
+        try:
+            for pid in sorted(blocks):
+                b = blocks[pid]
+                if b.nrows == 0:
+                    res[pid] = b
+                    continue
+                res[pid] = _filter_block(b, mask_of(b))
+                rows_in += b.nrows
+                kept += res[pid].nrows
+        finally:
+            if rng:
+                torch.cuda.nvtx.range_pop()
+        metrics.add("filter_rows_in", rows_in)
+        metrics.add("filter_rows_kept", kept)
+        return res
+
+    return DataFrame(df.schema, _Derived(df, compute), df.num_partitions)
+
+
+def _filter_block(b: Block, mask: torch.Tensor) -> Block:
+    """Rows of `b` whose mask entry is true, order kept. A device mask compacts
+    the device columns with the native kernels (dense columns 16 per call,
+    strings through the kept-row index); whatever lives on the host is
+    indexed there."""
+    from .._native import _C
+    cols: Dict[str, Any] = {}
+    dev_dense = [n for n, c in b.columns.items() if mask.is_cuda and isinstance(c, torch.Tensor)
+                 and c.device == mask.device and c.dim() >= 1]
+    if not dev_dense:
+        hm = mask.cpu() if mask.is_cuda else mask
+        idx = None
+        for n, c in b.columns.items():
+            if isinstance(c, torch.Tensor):
+                cols[n] = c[hm.to(c.device)] if c.is_cuda else c[hm]
+            else:
+                if idx is None:
+                    idx = torch.nonzero(hm).reshape(-1).numpy()
+                cols[n] = c.take(idx)
+        return Block(int(hm.sum().item()), cols)
+    others = [n for n in b.columns if n not in dev_dense]
+    index = None
+    total = 0
+    for g in range(0, len(dev_dense), _COMPACT_GROUP):
+        names = dev_dense[g:g + _COMPACT_GROUP]
+        outs, total, ix = _C.compact_rows(mask, [b.columns[n] for n in names], bool(others) and index is None)
+        index = ix if ix is not None else index
+        cols.update(zip(names, outs))
+    host_idx = hm = None
+    for n in others:
+        c = b.columns[n]
+        if isinstance(c, StringColumn) and c.is_cuda and c.device == mask.device:
+            offs, data = _C.gather_strings(c.offsets, c.data, index)
+            cols[n] = StringColumn(offs.to(mask.device), data, c.binary)
+        elif isinstance(c, torch.Tensor):
+            hm = mask.cpu() if hm is None else hm
+            cols[n] = c[hm.to(c.device)]
+        else:
+            if host_idx is None:
+                host_idx = index.cpu().numpy()
+            cols[n] = c.take(host_idx)
+    return Block(int(total), {n: cols[n] for n in b.columns})
 
 
 class GroupedData:
