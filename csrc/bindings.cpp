@@ -139,6 +139,8 @@ void set_conv_direct(int on);  // kernels/conv_direct.hip
 void set_pool_conv_fusion(bool on);  // runtime/executor.cpp
 }  // namespace tfa
 
+static thread_local int g_sort_last_passes = 0;  // radix passes of this thread's last sort_argsort
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "tensorframes_amd native runtime (GraphDef executor + HIP/CDNA4 kernels)";
 
@@ -700,6 +702,130 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("mask"), py::arg("cols"), py::arg("want_index") = false,
      "rows of the device columns whose mask entry is non-zero, in order -> (compacted columns, kept count, "
      "int64 indices of the kept rows or None); one stream synchronisation reads the count");
+  // DataFrame.orderBy / sortWithinPartitions on device-resident partitions (kernels/sort.hip)
+  m.def("sort_tile_rows", [] { return k::sort_tile_rows(); }, "keys per block of the radix sort under sort_argsort");
+  m.def("sort_encode", [](const std::vector<at::Tensor>& keys, const std::vector<bool>& descending) {
+    if (keys.empty() || keys.size() > static_cast<size_t>(k::kMaxSortKeys))
+      throw py::value_error(str_cat("sort_encode: 1..", k::kMaxSortKeys, " keys per call, got ", keys.size()));
+    if (descending.size() != keys.size())
+      throw py::value_error(str_cat("sort_encode: ", descending.size(), " directions for ", keys.size(), " keys"));
+    if (!keys[0].is_cuda()) throw py::value_error("sort_encode: the keys must be device tensors");
+    if (keys[0].dim() != 1) throw py::value_error("sort_encode: keys must be 1-D (one scalar per row)");
+    const int64_t n = keys[0].size(0);
+    k::SortKeys sk;
+    sk.n = static_cast<int>(keys.size());
+    std::vector<at::Tensor> keep;
+    for (size_t c = 0; c < keys.size(); ++c) {
+      const at::Tensor& t = keys[c];
+      if (!t.is_cuda() || t.device() != keys[0].device())
+        throw py::value_error(str_cat("sort_encode: key ", c, " is not on the first key's device"));
+      if (t.dim() != 1 || t.size(0) != n)
+        throw py::value_error(str_cat("sort_encode: key ", c, " must be 1-D with ", n, " rows"));
+      const auto st = t.scalar_type();
+      if (st != at::kFloat && st != at::kDouble && st != at::kLong && st != at::kInt && st != at::kShort &&
+          st != at::kChar && st != at::kByte && st != at::kBool)
+        throw py::type_error(str_cat("sort_encode: ", c10::toString(st), " is not supported as a sort key"));
+      keep.push_back(t.contiguous());
+      sk.dtype[c] = from_scalar_type(st);
+      sk.ptr[c] = keep.back().data_ptr();
+      sk.descending[c] = descending[c] ? 1 : 0;
+    }
+    c10::hip::HIPGuard guard(keys[0].device().index());
+    at::Tensor words = pool_empty({static_cast<int64_t>(keys.size()), n}, keys[0].options().dtype(at::kLong));
+    k::sort_encode(sk, n, words.data_ptr<int64_t>(), c10::hip::getCurrentHIPStream(keys[0].device().index()).stream());
+    return words;
+  }, py::arg("keys"), py::arg("descending"),
+     "device key columns [n] + a descending flag each -> int64 [keys, n]: one order-preserving unsigned word per "
+     "key and row (bit patterns)");
+  m.def("sort_argsort", [](const at::Tensor& words0) {
+    if (!words0.is_cuda() || words0.scalar_type() != at::kLong || words0.dim() != 2)
+      throw py::value_error("sort_argsort: device int64 words [W, n] expected");
+    if (words0.size(0) < 1 || words0.size(0) > k::kMaxSortKeys)
+      throw py::value_error(str_cat("sort_argsort: 1..", k::kMaxSortKeys, " words per row, got ", words0.size(0)));
+    c10::hip::HIPGuard guard(words0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(words0.device().index()).stream();
+    at::Tensor words = words0.contiguous();
+    const int W = static_cast<int>(words.size(0));
+    const int64_t n = words.size(1);
+    at::Tensor perm = pool_empty({n}, words.options());
+    g_sort_last_passes = 0;
+    if (n > 0) {
+      const size_t wsb = k::sort_argsort_workspace_bytes(W, n);
+      at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, words.options());
+      py::gil_scoped_release nogil;
+      g_sort_last_passes = k::sort_argsort(words.data_ptr<int64_t>(), W, n, perm.data_ptr<int64_t>(), ws.data_ptr(),
+                                           static_cast<size_t>(ws.numel()) * 8, s);
+    }
+    return perm;
+  }, py::arg("words"),
+     "words [W, n] (sort_encode) -> int64 perm [n]: perm[j] = source row of output row j, stable; only the 8-bit "
+     "digits that vary are sorted (one stream synchronisation reads the masks)");
+  m.def("sort_last_passes", [] { return g_sort_last_passes; },
+        "radix passes of the calling thread's last sort_argsort");
+  m.def("permute_rows", [](const at::Tensor& perm0, const std::vector<at::Tensor>& cols) {
+    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("permute_rows: 1..", k::kMaxPackCols, " columns per call, got ", cols.size()));
+    if (perm0.scalar_type() != at::kLong)
+      throw py::type_error(str_cat("permute_rows: the permutation must be int64, got ", c10::toString(perm0.scalar_type())));
+    if (!perm0.is_cuda()) throw py::value_error("permute_rows: the permutation must be a device tensor");
+    if (cols[0].dim() < 1) throw py::value_error("permute_rows: columns need a row dimension");
+    const int64_t n = cols[0].size(0);
+    if (perm0.dim() != 1 || perm0.size(0) != n)
+      throw py::value_error(str_cat("permute_rows: the permutation must hold one entry per row ([", n, "]), got ",
+                                    perm0.dim(), "-D with ", perm0.numel(), " entries"));
+    std::vector<at::Tensor> src;
+    for (size_t c = 0; c < cols.size(); ++c) {
+      const at::Tensor& t = cols[c];
+      if (!t.is_cuda() || t.device() != perm0.device())
+        throw py::value_error(str_cat("permute_rows: column ", c, " is not on the permutation's device"));
+      if (t.dim() < 1 || t.size(0) != n)
+        throw py::value_error(str_cat("permute_rows: column ", c, " has ", t.dim() < 1 ? 0 : t.size(0),
+                                      " rows, column 0 has ", n));
+      src.push_back(t.contiguous());
+    }
+    c10::hip::HIPGuard guard(perm0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(perm0.device().index()).stream();
+    at::Tensor perm = perm0.contiguous();
+    k::PackCols ps, pd;
+    ps.n = pd.n = static_cast<int>(src.size());
+    std::vector<at::Tensor> outs;
+    for (size_t c = 0; c < src.size(); ++c) {
+      at::Tensor o = pool_empty(src[c].sizes().vec(), src[c].options());
+      const int64_t rb = n ? src[c].numel() / n * static_cast<int64_t>(src[c].element_size()) : 0;
+      ps.row_bytes[c] = pd.row_bytes[c] = rb;
+      ps.off[c] = pd.off[c] = 0;
+      ps.ptr[c] = src[c].data_ptr();
+      pd.ptr[c] = o.data_ptr();
+      outs.push_back(o);
+    }
+    if (n > 0) k::permute_rows(ps, pd, perm.data_ptr<int64_t>(), n, s);
+    return outs;
+  }, py::arg("perm"), py::arg("cols"),
+     "output row j of every device column = its row perm[j] (perm: a device int64 permutation of the rows), all "
+     "columns in one launch");
+  m.def("sort_bounds", [](const at::Tensor& words0, const at::Tensor& perm0, const at::Tensor& splitters0) {
+    if (!words0.is_cuda() || words0.scalar_type() != at::kLong || words0.dim() != 2)
+      throw py::value_error("sort_bounds: device int64 words [W, n] expected");
+    const int64_t W = words0.size(0), n = words0.size(1);
+    if (W < 1 || W > k::kMaxSortKeys)
+      throw py::value_error(str_cat("sort_bounds: 1..", k::kMaxSortKeys, " words per row, got ", W));
+    if (!perm0.is_cuda() || perm0.device() != words0.device() || perm0.scalar_type() != at::kLong ||
+        perm0.dim() != 1 || perm0.size(0) != n)
+      throw py::value_error(str_cat("sort_bounds: a device int64 permutation [", n, "] on the words' device expected"));
+    if (splitters0.scalar_type() != at::kLong || splitters0.dim() != 2 || splitters0.size(1) != W)
+      throw py::value_error(str_cat("sort_bounds: int64 splitters [S, ", W, "] expected"));
+    c10::hip::HIPGuard guard(words0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(words0.device().index()).stream();
+    at::Tensor words = words0.contiguous(), perm = perm0.contiguous();
+    at::Tensor sp = splitters0.to(words0.device()).contiguous();
+    const int64_t S = sp.size(0);
+    at::Tensor out = pool_empty({S}, words.options());
+    k::sort_bounds(words.data_ptr<int64_t>(), static_cast<int>(W), n, perm.data_ptr<int64_t>(), sp.data_ptr<int64_t>(),
+                   S, out.data_ptr<int64_t>(), s);
+    return out;
+  }, py::arg("words"), py::arg("perm"), py::arg("splitters"),
+     "for each splitter tuple [W]: the number of rows of the sorted order whose word tuple is lexicographically "
+     "(unsigned) below it -> device int64 [S]");
   // native JPEG decode into one ragged (pinned) buffer (runtime/jpeg_decode.cpp)
   struct PyJpegBatch {
     std::vector<py::buffer_info> views;  // keep the cells' buffers exported while decoding

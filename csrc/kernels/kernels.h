@@ -165,6 +165,39 @@ int64_t compact_plan(const uint8_t* mask, int64_t n, void* workspace, size_t wor
 void compact_gather(const PackCols& src, const PackCols& dst, const uint8_t* mask, int64_t n, int64_t total,
                     const void* workspace, int64_t* index, hipStream_t s);
 
+// ------------------------------------------------------------ sort (sort.hip)
+// DataFrame.orderBy / sortWithinPartitions. Every sort key becomes one
+// unsigned 64-bit word per row whose unsigned order is the key's order (bool /
+// uint8: the value; signed ints: sign-extended, bit 63 flipped; floats: the
+// IEEE bits at the type's width with every NaN the canonical quiet NaN and
+// -0.0 as +0.0, negative values complemented, the others with the sign bit
+// set, a float32 word in the low 32 bits; a descending key is complemented at
+// its own width). Rows are ordered by the tuple of words; the sort is stable.
+constexpr int kMaxSortKeys = 8;
+struct SortKeys {
+  int n = 0;
+  DType dtype[kMaxSortKeys];
+  const void* ptr[kMaxSortKeys];  // [rows] each, contiguous
+  int descending[kMaxSortKeys];
+};
+// words [keys.n][n] (int64 bit patterns, word-major), every key in one launch
+void sort_encode(const SortKeys& keys, int64_t n, int64_t* words, hipStream_t s);
+int sort_tile_rows();  // radix::kTile
+size_t sort_argsort_workspace_bytes(int W, int64_t n);
+// perm[j] = source row of output row j under the (stable) order of the word
+// tuples: LSD over the words, and inside a word only over the 8-bit digits
+// that vary (one reduction finds them; the stream is synchronised once to
+// read the W masks). Returns the radix passes run.
+int sort_argsort(const int64_t* words, int W, int64_t n, int64_t* perm, void* workspace, size_t workspace_size,
+                 hipStream_t s);
+// dst.ptr[c] row j = src.ptr[c] row perm[j] for every column (rows of
+// row_bytes[c] bytes, `off` ignored); perm values must lie in [0, n)
+void permute_rows(const PackCols& src, const PackCols& dst, const int64_t* perm, int64_t n, hipStream_t s);
+// out[i] = rows of the sorted order (perm) whose word tuple is < splitters[i]
+// ([S][W], row-major), lexicographically as unsigned words
+void sort_bounds(const int64_t* words, int W, int64_t n, const int64_t* perm, const int64_t* splitters, int64_t S,
+                 int64_t* out, hipStream_t s);
+
 // ------------------------------------------------------------ data movement
 // dst[idx] = src[idx] over `dims`, both operands addressed by element strides
 // (src strides may be 0 or negative; pointers already include the offsets).

@@ -242,15 +242,19 @@ size_t sort_ws_bytes(int64_t n) {
          scan_ws_bytes<uint32_t>(cnt);
 }
 
-// stable sort of (keys, vals) by key bits [0, bits); results in keys_out /
-// vals_out (which must not alias the inputs). vals_in == nullptr sorts
-// (key, index) pairs.
+// stable sort of (keys, vals) by the 8-bit digits at bit positions shifts[0],
+// shifts[1], ... (least significant first; nshifts >= 1), one pass per digit;
+// results in keys_out / vals_out (which must not alias the inputs). vals_in ==
+// nullptr sorts (key, index) pairs.
 template <typename K, typename V>
-void sort_pairs(const K* keys_in, const V* vals_in, K* keys_out, V* vals_out, int64_t n, int bits, void* ws,
-                size_t ws_size, hipStream_t s) {
+void sort_pairs_digits(const K* keys_in, const V* vals_in, K* keys_out, V* vals_out, int64_t n, const int* shifts,
+                       int nshifts, void* ws, size_t ws_size, hipStream_t s) {
   const size_t need = sort_ws_bytes<K, V>(n);
   TFA_CHECK(ws_size >= need, "radix sort: workspace too small");
   TFA_CHECK(n < (int64_t(1) << 32) - 1, "radix sort: more than 2^32 keys");
+  TFA_CHECK(nshifts >= 1, "radix sort: no digit to sort by");
+  for (int i = 0; i < nshifts; ++i)
+    TFA_CHECK(shifts[i] >= 0 && shifts[i] < int(sizeof(K) * 8), "radix sort: digit shift ", shifts[i], " out of range");
   if (n <= 0) return;
   const int64_t nt = tiles(n);
   TFA_CHECK(nt <= 0x7fffffff, "radix sort: too many tiles");
@@ -262,8 +266,7 @@ void sort_pairs(const K* keys_in, const V* vals_in, K* keys_out, V* vals_out, in
   uint32_t* counts = reinterpret_cast<uint32_t*>(p);
   p += align_up((int64_t)kRadix * nt * sizeof(uint32_t));
   void* scan_ws = p;
-  bits = std::max(1, std::min(bits, int(sizeof(K) * 8)));
-  const int passes = (bits + kBits - 1) / kBits;
+  const int passes = nshifts;
   const K* kin = keys_in;
   const V* vin = vals_in;
   for (int ps = 0; ps < passes; ++ps) {
@@ -271,7 +274,7 @@ void sort_pairs(const K* keys_in, const V* vals_in, K* keys_out, V* vals_out, in
     const bool to_out = ((passes - 1 - ps) % 2) == 0;
     K* kout = to_out ? keys_out : kalt;
     V* vout = to_out ? vals_out : valt;
-    const int shift = ps * kBits;
+    const int shift = shifts[ps];
     hipLaunchKernelGGL((hist_kernel<K>), dim3((unsigned)nt), dim3(kThreads), 0, s, kin, n, shift, counts, nt);
     scan<uint32_t>(counts, counts, (int64_t)kRadix * nt, false, scan_ws, s);
     hipLaunchKernelGGL((scatter_kernel<K, V>), dim3((unsigned)nt), dim3(kThreads), 0, s, kin, vin, kout, vout, n,
@@ -279,6 +282,17 @@ void sort_pairs(const K* keys_in, const V* vals_in, K* keys_out, V* vals_out, in
     kin = kout;
     vin = vout;
   }
+}
+
+// stable sort of (keys, vals) by key bits [0, bits): every digit below `bits`
+template <typename K, typename V>
+void sort_pairs(const K* keys_in, const V* vals_in, K* keys_out, V* vals_out, int64_t n, int bits, void* ws,
+                size_t ws_size, hipStream_t s) {
+  bits = std::max(1, std::min(bits, int(sizeof(K) * 8)));
+  const int passes = (bits + kBits - 1) / kBits;
+  int shifts[sizeof(K)];
+  for (int ps = 0; ps < passes; ++ps) shifts[ps] = ps * kBits;
+  sort_pairs_digits<K, V>(keys_in, vals_in, keys_out, vals_out, n, shifts, passes, ws, ws_size, s);
 }
 
 }  // namespace radix

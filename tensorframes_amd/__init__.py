@@ -23,7 +23,7 @@ from .core import (InputNotFoundException, InvalidDimensionException, InvalidTyp
                    map_rows, print_schema, reduce_blocks, reduce_rows, row)
 from .frame.column_info import (SHAPE_KEY, TYPE_KEY, ColumnInformation, DataFrameInfo, HighDimException,
                                 SparkTFColInfo)
-from .frame.column import Column, col, column
+from .frame.column import Column, asc, col, column, desc
 from .frame.dataframe import (DataFrame, GroupedData, create_dataframe, createDataFrame, from_columns,
                               generate, tensor_field)
 from .frame.arrow_io import from_arrow, read_parquet, to_arrow, write_parquet

@@ -1,5 +1,5 @@
 """Column expressions: `df.x`, `df["x"]`, `col("x")`, arithmetic, comparisons,
-`&` / `|` / `~`, `.alias()`, `.cast()`.
+`&` / `|` / `~`, `.alias()`, `.cast()`, `.asc()` / `.desc()`.
 
 A `Column` is a small expression tree over the columns of a frame. It holds
 no data; `DataFrame.select` / `withColumn` / `filter` compile it, through the
@@ -17,6 +17,10 @@ the other (a scalar column against a vector column compares row by row), and
 `.sum()` / `.min()` / `.max()` / `.mean()` / `.all()` / `.any()` reduce over
 the cell, which is how a predicate over a vector column yields one value per
 row.
+
+`.asc()` / `.desc()` mark a Column as a sort order for `DataFrame.orderBy` /
+`sort` / `sortWithinPartitions`; such a Column is no value: `select`,
+`withColumn`, `filter` and every operator refuse it (`InvalidTypeException`).
 """
 from __future__ import annotations
 
@@ -51,12 +55,13 @@ def _is_literal(v) -> bool:
 class Column:
     """An expression over the columns of a DataFrame (see the module docstring)."""
 
-    __slots__ = ("_expr", "_alias")
+    __slots__ = ("_expr", "_alias", "_order")
     __hash__ = None  # `==` builds an expression: columns are not hashable
 
-    def __init__(self, expr: tuple, alias: Optional[str] = None):
+    def __init__(self, expr: tuple, alias: Optional[str] = None, order: Optional[str] = None):
         self._expr = expr
         self._alias = alias
+        self._order = order  # "asc" / "desc": a sort order (orderBy / sort / sortWithinPartitions only)
 
     # -- construction
     @staticmethod
@@ -71,12 +76,13 @@ class Column:
     def alias(self, name: str) -> "Column":
         if not isinstance(name, str) or not name:
             raise TypeError(f"alias: a non-empty column name is expected, got {name!r}")
-        return Column(self._expr, name)
+        return Column(self._expr, name, self._order)
 
     name = alias
 
     def cast(self, to) -> "Column":
         """`to`: a numeric SQL type or "double" | "float" | "int" | "bigint"."""
+        self._no_sort_order("cast")
         t = sql_type_from_string(to) if isinstance(to, str) else to
         if isinstance(t, type) and issubclass(t, DataType):
             t = t()
@@ -86,6 +92,26 @@ class Column:
         return Column(("cast", self._expr, t.tf_dtype), self._alias)
 
     astype = cast
+
+    # -- sort orders
+    def asc(self) -> "Column":
+        """This expression as an ascending sort key (NaN after +inf, -0.0 == 0.0)."""
+        return Column(self._expr, self._alias, "asc")
+
+    def desc(self) -> "Column":
+        """This expression as a descending sort key."""
+        return Column(self._expr, self._alias, "desc")
+
+    @property
+    def sort_order(self) -> Optional[str]:
+        """"asc" / "desc" for a Column made by .asc() / .desc(), else None."""
+        return self._order
+
+    def _no_sort_order(self, where: str) -> None:
+        if self._order is not None:
+            raise _errors().InvalidTypeException(
+                f"{where}: '{self.output_name}.{self._order}()' is a sort order, not a value; it is accepted only "
+                f"by orderBy / sort / sortWithinPartitions")
 
     # -- naming
     @property
@@ -102,7 +128,9 @@ class Column:
 
     # -- operators
     def _binary(self, op: str, other, reflected: bool = False) -> "Column":
+        self._no_sort_order(f"operator '{_ARITH.get(op) or _COMPARE.get(op) or _LOGICAL[op]}'")
         if isinstance(other, Column):
+            other._no_sort_order(f"operator '{_ARITH.get(op) or _COMPARE.get(op) or _LOGICAL[op]}'")
             o = other._expr
         elif _is_literal(other):
             o = ("lit", other)
@@ -137,6 +165,7 @@ class Column:
         return self._binary("div", o, True)
 
     def __neg__(self):
+        self._no_sort_order("unary '-'")
         expr = ("un", "neg", self._expr)
         _typeof(expr, None)
         return Column(expr)
@@ -172,6 +201,7 @@ class Column:
         return self._binary("or", o, True)
 
     def __invert__(self):
+        self._no_sort_order("operator '~'")
         expr = ("un", "not", self._expr)
         _typeof(expr, None)
         return Column(expr)
@@ -181,6 +211,7 @@ class Column:
                          "'~' for 'not' when building DataFrame boolean expressions.")
 
     def _reduce(self, op: str) -> "Column":
+        self._no_sort_order(f"{op}()")
         expr = ("red", op, self._expr)
         _typeof(expr, None)
         return Column(expr)
@@ -214,6 +245,16 @@ def col(name: str) -> Column:
 
 
 column = col
+
+
+def asc(name: str) -> Column:
+    """`col(name).asc()`: an ascending sort key for orderBy / sort / sortWithinPartitions."""
+    return col(name).asc()
+
+
+def desc(name: str) -> Column:
+    """`col(name).desc()`: a descending sort key."""
+    return col(name).desc()
 
 
 # ------------------------------------------------------------------ analysis

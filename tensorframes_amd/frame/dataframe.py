@@ -420,6 +420,7 @@ class DataFrame:
                 it = Column._ref(it)
             elif not isinstance(it, Column):
                 raise TypeError(f"select: a column name or a Column is expected, got {type(it).__name__}")
+            it._no_sort_order("select")
             if it.is_reference:
                 src = it._expr[1]
                 if src not in self._schema:
@@ -456,6 +457,7 @@ class DataFrame:
         in place (keeps its position), as in Spark."""
         if not isinstance(expr, Column):
             raise TypeError(f"withColumn: a Column expression is expected, got {type(expr).__name__}")
+        expr._no_sort_order("withColumn")
         new = expr.alias(name)
         if name in self._schema:
             return self._select_columns([new if c == name else c for c in self.columns])
@@ -484,6 +486,7 @@ class DataFrame:
         mask comes back."""
         if not isinstance(cond, Column):
             raise TypeError(f"filter: a boolean Column is expected (e.g. df.x > 3), got {type(cond).__name__}")
+        cond._no_sort_order("filter")
         return _filter_frame(self, cond)
 
     where = filter
@@ -508,6 +511,30 @@ class DataFrame:
                 before += counts[p]
             return res
         return DataFrame(self._schema, _Derived(self, fn, streamable=False), nparts)
+
+    def sortWithinPartitions(self, *cols, ascending=True) -> "DataFrame":  # noqa: N802
+        """Every partition sorted on its own by the keys `cols` (names or
+        Columns, `.asc()` / `.desc()` or `ascending=` a bool or one bool per
+        key); schema, metadata and the number of partitions are unchanged
+        (partition-local: no collectives). The sort is stable; NaN sorts after
+        +inf, -0.0 equals 0.0. Device-resident partitions are sorted on the
+        device (kernels/sort.hip)."""
+        return _sort_frame(self, cols, ascending, False, "sortWithinPartitions")
+
+    sort_within_partitions = sortWithinPartitions
+
+    def orderBy(self, *cols, ascending=True) -> "DataFrame":  # noqa: N802
+        """The rows in the global order of the keys `cols` (see
+        `sortWithinPartitions` for the keys): the number of partitions is
+        unchanged and reading them in order gives the sorted rows. Rows with
+        equal keys keep their input order (partition order, then row order),
+        so the result does not depend on the number of ranks. A sample sort:
+        local sort, agreed splitters, one exchange of contiguous slices, local
+        sort of what arrived."""
+        return _sort_frame(self, cols, ascending, True, "orderBy")
+
+    sort = orderBy
+    order_by = orderBy
 
     def drop(self, *names) -> "DataFrame":
         return self.select([n for n in self.columns if n not in names])
@@ -718,6 +745,262 @@ def _filter_block(b: Block, mask: torch.Tensor) -> Block:
                 host_idx = index.cpu().numpy()
             cols[n] = c.take(host_idx)
     return Block(int(total), {n: cols[n] for n in b.columns})
+
+
+# ------------------------------------------------------------------ sort
+_PERMUTE_GROUP = 16  # columns per _C.permute_rows call (kernels.h kMaxPackCols)
+_MAX_SORT_KEYS = 8   # kernels.h kMaxSortKeys
+_SORT_SAMPLES_PER_PARTITION = 4  # orderBy: samples a partition gives, times the partition count
+_SORT_KEY_DTYPES = (D.DT_BOOL, D.DT_UINT8, D.DT_INT8, D.DT_INT16, D.DT_INT32, D.DT_INT64, D.DT_FLOAT, D.DT_DOUBLE)
+
+
+def _host_sort_words(key: torch.Tensor, descending: bool) -> np.ndarray:
+    """The order-preserving unsigned 64-bit word of every row of one key
+    column, on the host (the same table as kernels/sort.hip)."""
+    a = key.detach().cpu().contiguous().numpy()
+    if a.dtype == np.float32:
+        b = a.view(np.uint32).copy()
+        b[np.isnan(a)] = 0x7FC00000
+        b[b == 0x80000000] = 0
+        neg = (b >> 31).astype(bool)
+        w = np.where(neg, ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+        return (~w if descending else w).astype(np.uint64)
+    if a.dtype == np.float64:
+        b = a.view(np.uint64).copy()
+        b[np.isnan(a)] = 0x7FF8000000000000
+        b[b == 0x8000000000000000] = 0
+        neg = (b >> 63).astype(bool)
+        w = np.where(neg, ~b, b | np.uint64(0x8000000000000000)).astype(np.uint64)
+    elif a.dtype in (np.bool_, np.uint8):
+        w = a.astype(np.uint64)
+    else:
+        w = a.astype(np.int64).view(np.uint64) ^ np.uint64(0x8000000000000000)
+    return ~w if descending else w
+
+
+def _sort_order_of(b: Block, keys: Sequence[str], desc: Sequence[bool]):
+    """(words [W, n], perm [n], radix passes) of one partition: the stable
+    order of its rows by the key tuples. Device tensors when every key column
+    is on one device (encode + radix argsort kernels), numpy arrays otherwise
+    (the same words, np.lexsort: the CPU oracle)."""
+    from .. import core
+    from .._native import _C
+    if b.nrows == 0:
+        return np.zeros((len(keys), 0), dtype=np.uint64), np.zeros(0, dtype=np.int64), 0
+    cols = [b.columns[k] for k in keys]
+    for k, c in zip(keys, cols):
+        if not isinstance(c, torch.Tensor) or c.dim() != 1:
+            raise core.InvalidDimensionException(
+                f"sort: the key column '{k}' does not hold one scalar per row in this partition; reduce the cell "
+                f"first (.sum(), .max(), ...)")
+    if all(c.is_cuda for c in cols) and len({c.device for c in cols}) == 1:
+        words = _C.sort_encode(cols, [bool(d) for d in desc])
+        perm = _C.sort_argsort(words)
+        return words, perm, int(_C.sort_last_passes())
+    words = np.stack([_host_sort_words(c, d) for c, d in zip(cols, desc)], 0)
+    perm = np.lexsort(words[::-1])  # (stable; the last key given to lexsort is the primary one)
+    return words, perm.astype(np.int64), 0
+
+
+def _permute_block(b: Block, perm) -> Block:
+    """Rows of `b` in the order perm (a device int64 tensor or a numpy array):
+    device dense columns through the row-permute kernel, 16 per call, device
+    strings through the string gather; whatever lives on the host is indexed
+    there."""
+    from .._native import _C
+    cols: Dict[str, Any] = {}
+    on_dev = isinstance(perm, torch.Tensor) and perm.is_cuda
+    dev_dense = [n for n, c in b.columns.items() if on_dev and isinstance(c, torch.Tensor)
+                 and c.device == perm.device and c.dim() >= 1]
+    for g in range(0, len(dev_dense), _PERMUTE_GROUP):
+        names = dev_dense[g:g + _PERMUTE_GROUP]
+        cols.update(zip(names, _C.permute_rows(perm, [b.columns[n] for n in names])))
+    host_t = host_np = None
+    for n, c in b.columns.items():
+        if n in cols:
+            continue
+        if host_t is None:
+            host_t = perm.cpu() if isinstance(perm, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(perm))
+            host_np = host_t.numpy()
+        if isinstance(c, StringColumn) and c.is_cuda:
+            idx = perm if on_dev and perm.device == c.device else host_t.to(c.device)
+            offs, data = _C.gather_strings(c.offsets, c.data, idx)
+            cols[n] = StringColumn(offs.to(c.device), data, c.binary)
+        elif isinstance(c, torch.Tensor):
+            cols[n] = c.index_select(0, host_t.to(c.device))
+        else:
+            cols[n] = c.take(host_np)
+    return Block(b.nrows, {n: cols[n] for n in b.columns})
+
+
+def _sort_block(b: Block, keys: Sequence[str], desc: Sequence[bool], stats: List[int]):
+    """(sorted block, words, perm) of one partition; words / perm are None for
+    a partition of fewer than two rows only when they are not needed."""
+    words, perm, passes = _sort_order_of(b, keys, desc)
+    stats[0] += b.nrows
+    stats[1] += passes
+    return (_permute_block(b, perm) if b.nrows > 1 else b), words, perm
+
+
+def _lower_bounds(words, perm, splitters: np.ndarray) -> List[int]:
+    """For each splitter tuple [S, W] (uint64): the rows of the sorted order
+    whose word tuple is lexicographically below it."""
+    from .._native import _C
+    if len(splitters) == 0:
+        return []
+    if isinstance(words, torch.Tensor):
+        sp = torch.from_numpy(np.ascontiguousarray(splitters).view(np.int64))
+        return _C.sort_bounds(words, perm, sp).cpu().tolist()
+    sw = words[:, perm]  # [W, n] in sorted order
+    n = sw.shape[1]
+    out = []
+    for t in splitters:
+        lo, hi = 0, n
+        for w in range(sw.shape[0]):  # narrow [lo, hi) to the rows equal to the splitter's prefix
+            seg = sw[w, lo:hi]
+            a = lo + int(np.searchsorted(seg, t[w], side="left"))
+            hi = lo + int(np.searchsorted(seg, t[w], side="right"))
+            lo = a
+            if lo == hi:
+                break
+        out.append(lo)
+    return out
+
+
+def _order_blocks(blocks: Dict[int, Block], names: Sequence[str], schema: StructType, nparts: int,
+                  keys: Sequence[str], desc: Sequence[bool], stats: List[int]) -> Dict[int, Block]:
+    """orderBy's sample sort over this rank's partitions (collective)."""
+    from ..parallel import frame_comm
+    W = len(keys)
+    local: Dict[int, Block] = {}
+    order: Dict[int, tuple] = {}
+    samples = []
+    m = _SORT_SAMPLES_PER_PARTITION * nparts
+    for pid in sorted(blocks):
+        local[pid], words, perm = _sort_block(blocks[pid], keys, desc, stats)
+        order[pid] = (words, perm)
+        n = blocks[pid].nrows
+        if n:
+            # evenly spaced rows of the sorted order (no RNG: the same on every run)
+            take = min(n, m)
+            pos = np.array([((2 * j + 1) * n) // (2 * take) for j in range(take)], dtype=np.int64)
+            if isinstance(words, torch.Tensor):
+                rows = perm[torch.from_numpy(pos).to(perm.device)]
+                samples.append(words[:, rows].cpu().numpy().view(np.uint64).T)
+            else:
+                samples.append(words[:, perm[pos]].T)
+    mine = np.concatenate(samples, 0) if samples else np.zeros((0, W), dtype=np.uint64)
+    every = np.concatenate(dist.all_gather_object(mine), 0) if dist.is_distributed() else mine
+    if len(every):
+        every = every[np.lexsort(every.T[::-1])]
+        splitters = np.stack([every[(q * len(every)) // nparts] for q in range(1, nparts)], 0) \
+            if nparts > 1 else np.zeros((0, W), dtype=np.uint64)
+    else:
+        splitters = np.zeros((0, W), dtype=np.uint64)
+    # contiguous slices of every sorted local partition, one per output partition
+    table = torch.zeros((nparts, max(nparts, 1)), dtype=torch.int64)
+    for pid, b in local.items():
+        cuts = [0] + (_lower_bounds(*order[pid], splitters) if b.nrows else [0] * (nparts - 1)) + [b.nrows]
+        for q in range(nparts):
+            table[pid, q] = cuts[q + 1] - cuts[q]
+    dist.all_reduce_host_(table, "Sum")  # (every rank fills the rows of its own partitions)
+    pieces: Dict[int, List[tuple]] = {}
+    for p, lens in enumerate(table.tolist()):
+        start, pieces[p] = 0, []
+        for q in range(nparts):
+            if lens[q]:
+                pieces[p].append((q, start, lens[q]))
+            start += lens[q]
+    got = frame_comm.exchange_pieces(local, names, schema, nparts, pieces, stay_local=True)
+    # the pieces arrived in source-partition order: one more stable sort per block
+    return {q: _sort_block(b, keys, desc, stats)[0] for q, b in got.items()}
+
+
+def _sort_frame(df: DataFrame, cols: Sequence[Any], ascending, global_order: bool, what: str) -> DataFrame:
+    """The lazy frame of orderBy / sortWithinPartitions: everything is
+    validated here (typed errors); computed keys become temporary columns
+    (through the select path) that are projected away afterwards."""
+    from .. import core
+    from ..utils.logging import metrics
+    items = [c for cs in cols for c in (cs if isinstance(cs, (list, tuple)) else [cs])]
+    if not items:
+        raise ValueError(f"{what}: at least one sort key is expected")
+    if len(items) > _MAX_SORT_KEYS:
+        raise ValueError(f"{what}: at most {_MAX_SORT_KEYS} sort keys, got {len(items)}")
+    if isinstance(ascending, (bool, np.bool_)):
+        asc = [bool(ascending)] * len(items)
+    elif isinstance(ascending, (list, tuple)) and all(isinstance(a, (bool, np.bool_, int)) for a in ascending):
+        if len(ascending) != len(items):
+            raise ValueError(f"{what}: ascending holds {len(ascending)} entries for {len(items)} sort keys")
+        asc = [bool(a) for a in ascending]
+    else:
+        raise TypeError(f"{what}: ascending must be a bool or a list of one bool per key, got {ascending!r}")
+    keys: List[str] = []
+    desc: List[bool] = []
+    extra: List[Column] = []
+    taken = set(df.columns)
+    for it, a in zip(items, asc):
+        if isinstance(it, str):
+            it = Column._ref(it)
+        elif not isinstance(it, Column):
+            raise TypeError(f"{what}: a column name or a Column is expected, got {type(it).__name__}")
+        desc.append((it.sort_order == "desc") if it.sort_order is not None else not a)
+        if it.is_reference:
+            if it._expr[1] not in df.schema:
+                raise ValueError(f"{what}: column {it._expr[1]} not found in {df.columns}")
+            keys.append(it._expr[1])
+        else:
+            k = 0
+            while f"tfa_sort_key_{k}" in taken:
+                k += 1
+            taken.add(f"tfa_sort_key_{k}")
+            keys.append(f"tfa_sort_key_{k}")
+            extra.append(Column(it._expr, f"tfa_sort_key_{k}"))
+    base = df._select_columns(list(df.columns) + extra) if extra else df
+    for k, it in zip(keys, items):
+        shown = it if isinstance(it, str) else it.output_name
+        f = base.schema[k]
+        if isinstance(f.dataType, (StringType, BinaryType)):
+            raise core.InvalidTypeException(
+                f"{what}: '{shown}' is a {type(f.dataType).__name__[:-4].lower()} column; string and binary "
+                f"columns are not supported as sort keys yet")
+        stf = ColumnInformation(f).stf
+        if stf is None:
+            raise core.InvalidTypeException(f"{what}: the type of '{shown}' ({f.dataType}) is not supported as a "
+                                            f"sort key")
+        if stf.tf_dtype in (D.DT_HALF, D.DT_BFLOAT16):
+            raise core.InvalidTypeException(f"{what}: '{shown}' is {D.dtype_name(stf.tf_dtype)}; half and bfloat16 "
+                                            f"columns are not supported as sort keys yet (cast to float)")
+        if stf.tf_dtype not in _SORT_KEY_DTYPES:
+            raise core.InvalidTypeException(f"{what}: '{shown}' is {D.dtype_name(stf.tf_dtype)}, which is not "
+                                            f"supported as a sort key")
+        if stf.shape.num_dims != 1:
+            raise core.InvalidDimensionException(
+                f"{what}: the key '{shown}' holds a cell of rank {max(stf.shape.num_dims - 1, 0)} per row, not a "
+                f"scalar; reduce the cell first (.sum(), .max(), ...)")
+    names = base.columns
+    schema = base.schema
+    nparts = df.num_partitions
+
+    def compute(blocks: Dict[int, Block]) -> Dict[int, Block]:
+        stats = [0, 0]  # rows sorted, radix passes
+        rng = torch.cuda.is_initialized()
+        if rng:
+            torch.cuda.nvtx.range_push("tfa.sort")
+        try:
+            if global_order:
+                res = _order_blocks(blocks, names, schema, nparts, keys, desc, stats)
+            else:
+                res = {pid: _sort_block(b, keys, desc, stats)[0] for pid, b in blocks.items()}
+        finally:
+            if rng:
+                torch.cuda.nvtx.range_pop()
+        metrics.add("sort_rows", stats[0])
+        metrics.add("sort_radix_passes", stats[1])
+        return res
+
+    out = DataFrame(schema, _Derived(base, compute, streamable=not global_order), nparts)
+    return out._project([(c, c) for c in df.columns]) if extra else out
 
 
 class GroupedData:

@@ -315,9 +315,6 @@ def repartition_blocks(local: Dict[int, Any], names: Sequence[str], schema, npar
     rank receives only the rows of the partitions it owns: dense columns in
     one all-to-all per column (RCCL for device-resident frames), other
     columns as pickled values."""
-    from ..frame.block import Block, build_column, column_tf_dtype, column_values
-    from .. import engine
-    w, me = dist.world_size(), dist.rank()
     counts = partition_rows({p: b.nrows for p, b in local.items()}, nparts_in)
     offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     total = int(offs[-1])
@@ -333,17 +330,40 @@ def repartition_blocks(local: Dict[int, Any], names: Sequence[str], schema, npar
                 res.append((q, lo - a0, hi - lo))
         return res
 
+    return exchange_pieces(local, names, schema, nparts_out, {p: pieces_of(p) for p in range(nparts_in)})
+
+
+def exchange_pieces(local: Dict[int, Any], names: Sequence[str], schema, nparts_out: int,
+                    pieces: Dict[int, List[Tuple[int, int, int]]], stay_local: bool = False) -> Dict[int, Any]:
+    """The exchange under `repartition` and `orderBy`. `pieces[p]` lists, for
+    EVERY input partition p (the same table on every rank), the contiguous row
+    slices (q, start within p, length) that go to output partition q. Each
+    rank receives the pieces of the partitions q it owns (q % world) and
+    concatenates them in source-partition order: dense columns in one
+    all-to-all per column (RCCL for device-resident frames), string columns
+    through `shuffle_strings`, other columns as pickled values. `stay_local`:
+    outside torch.distributed, dense and string columns stay on the device
+    they are on (they are not staged through the host)."""
+    from ..frame.block import Block, StringColumn, build_column, column_tf_dtype, column_values
+    from .. import engine
+    w, me = dist.world_size(), dist.rank()
+    nparts_in = len(pieces)
+    out_rows = [0] * nparts_out
+    for p in range(nparts_in):
+        for q, _, ln in pieces[p]:
+            out_rows[q] += ln
+
     # what this rank sends to each rank r, ordered by (q, p)
     send: List[List[Tuple[int, int, int, int]]] = [[] for _ in range(w)]  # (q, p, start, len)
     for p in sorted(local):
-        for q, st, ln in pieces_of(p):
+        for q, st, ln in pieces[p]:
             send[q % w].append((q, p, st, ln))
     for r in range(w):
         send[r].sort()
     # what this rank receives from each source rank s, in s's send order
     recv: List[List[Tuple[int, int, int, int]]] = [[] for _ in range(w)]
     for p in range(nparts_in):
-        for q, st, ln in pieces_of(p):
+        for q, st, ln in pieces[p]:
             if q % w == me:
                 recv[p % w].append((q, p, st, ln))
     for s in range(w):
@@ -354,22 +374,30 @@ def repartition_blocks(local: Dict[int, Any], names: Sequence[str], schema, npar
     mine = [q for q in range(nparts_out) if q % w == me]
     cols_out: Dict[int, Dict[str, Any]] = {q: {} for q in mine}
     devs = _agreed_devices(local, [n for n in names if kinds[n] is not None])
+    stay_local = stay_local and not dist.is_distributed()
+
+    def local_device(n: str):
+        """The one device every local non-empty block holds column n on (else the host)."""
+        ds = {local[p].columns[n].device for p in local if local[p].nrows}
+        return ds.pop() if len(ds) == 1 else torch.device("cpu")
+
     for n in names:
         kind = kinds[n]
         if kind is not None:
-            dev = devs[n]
+            dev = local_device(n) if stay_local else devs[n]
             parts = [local[p].columns[n][st:st + ln].to(dev) for r in range(w) for (_, p, st, ln) in send[r]]
             buf = engine.cat_rows(parts) if parts else engine.device_empty((0,) + kind[1], kind[0], dev)
             got = dist.all_to_all_rows(buf, send_rows, recv_rows) if dist.is_distributed() else buf
-            pos, pieces = 0, {q: [] for q in mine}
+            pos, got_pieces = 0, {q: [] for q in mine}
             for s in range(w):
                 for (q, p, st, ln) in recv[s]:
-                    pieces[q].append((p, got[pos:pos + ln]))
+                    got_pieces[q].append((p, got[pos:pos + ln]))
                     pos += ln
             for q in mine:
-                ps = [t for _, t in sorted(pieces[q], key=lambda x: x[0])]
+                ps = [t for _, t in sorted(got_pieces[q], key=lambda x: x[0])]
                 cols_out[q][n] = engine.cat_rows(ps) if ps else engine.device_empty((0,) + kind[1], kind[0], dev)
-        elif is_bytes_field(schema[n]) and dist.is_distributed():
+        elif is_bytes_field(schema[n]) and (dist.is_distributed() or (
+                stay_local and all(isinstance(local[p].columns[n], StringColumn) for p in local))):
             from ..frame.block import concat_columns
             from ..frame.types import BinaryType
             from ..ops import groupby as G
@@ -378,15 +406,19 @@ def repartition_blocks(local: Dict[int, Any], names: Sequence[str], schema, npar
             for r in range(w):
                 ps = [G.as_string_column(local[p].columns[n], binary).slice(st, st + ln) for (_, p, st, ln) in send[r]]
                 per_dest.append(concat_columns(ps) if ps else None)
-            got = shuffle_strings(per_dest, recv_rows, binary)
-            pos, pieces = 0, {q: [] for q in mine}
+            if dist.is_distributed():
+                got = shuffle_strings(per_dest, recv_rows, binary)
+            else:
+                got = per_dest[0] if per_dest[0] is not None else _empty_strings(binary)
+            pos, got_pieces = 0, {q: [] for q in mine}
             for s_ in range(w):
                 for (q, p, st, ln) in recv[s_]:
-                    pieces[q].append((p, got.slice(pos, pos + ln)))
+                    got_pieces[q].append((p, got.slice(pos, pos + ln)))
                     pos += ln
+            dev = local_device(n) if stay_local and local else torch.device("cpu")
             for q in mine:
-                ps = [c for _, c in sorted(pieces[q], key=lambda x: x[0])]
-                cols_out[q][n] = concat_columns(ps) if ps else _empty_strings(binary)
+                ps = [c for _, c in sorted(got_pieces[q], key=lambda x: x[0])]
+                cols_out[q][n] = (concat_columns(ps) if ps else _empty_strings(binary)).to(dev)
         else:
             tfd = _schema_tf(schema[n])
             if tfd is None:
@@ -394,11 +426,11 @@ def repartition_blocks(local: Dict[int, Any], names: Sequence[str], schema, npar
             payload = [[column_values(local[p].columns[n])[st:st + ln] for (_, p, st, ln) in send[r]]
                        for r in range(w)]
             got = dist.all_to_all_objects(payload) if dist.is_distributed() else payload
-            pieces = {q: [] for q in mine}
+            got_pieces = {q: [] for q in mine}
             for s in range(w):
                 for (q, p, st, ln), vals in zip(recv[s], got[s]):
-                    pieces[q].append((p, vals))
+                    got_pieces[q].append((p, vals))
             for q in mine:
-                vals = [v for _, vs in sorted(pieces[q], key=lambda x: x[0]) for v in vs]
+                vals = [v for _, vs in sorted(got_pieces[q], key=lambda x: x[0]) for v in vs]
                 cols_out[q][n] = build_column(vals, tfd)
-    return {q: Block(qb[q + 1] - qb[q], cols_out[q]) for q in mine}
+    return {q: Block(out_rows[q], cols_out[q]) for q in mine}

@@ -22,7 +22,7 @@ import contextlib
 from typing import Optional, Sequence
 
 from . import core
-from .frame.column import Column, col  # noqa: F401  (org.apache.spark.sql.functions.col next to the DSL)
+from .frame.column import Column, asc, col, desc  # noqa: F401  (org.apache.spark.sql.functions col / asc / desc next to the DSL)
 from .frame.column_info import HighDimException  # noqa: F401  (re-exported, as in dsl/package.scala)
 from .graph import dsl as tf
 
