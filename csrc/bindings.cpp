@@ -826,6 +826,132 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("words"), py::arg("perm"), py::arg("splitters"),
      "for each splitter tuple [W]: the number of rows of the sorted order whose word tuple is lexicographically "
      "(unsigned) below it -> device int64 [S]");
+  m.def("take_rows", [](const at::Tensor& idx0, const std::vector<at::Tensor>& cols) {
+    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("take_rows: 1..", k::kMaxPackCols, " columns per call, got ", cols.size()));
+    if (idx0.scalar_type() != at::kLong)
+      throw py::type_error(str_cat("take_rows: the row indices must be int64, got ", c10::toString(idx0.scalar_type())));
+    if (!idx0.is_cuda()) throw py::value_error("take_rows: the row indices must be a device tensor");
+    if (idx0.dim() != 1) throw py::value_error(str_cat("take_rows: the row indices must be 1-D, got ", idx0.dim(), "-D"));
+    if (cols[0].dim() < 1) throw py::value_error("take_rows: columns need a row dimension");
+    const int64_t n_src = cols[0].size(0), n_out = idx0.size(0);
+    if (n_out > 0 && n_src == 0) throw py::value_error("take_rows: rows asked of columns without rows");
+    std::vector<at::Tensor> src;
+    for (size_t c = 0; c < cols.size(); ++c) {
+      const at::Tensor& t = cols[c];
+      if (!t.is_cuda() || t.device() != idx0.device())
+        throw py::value_error(str_cat("take_rows: column ", c, " is not on the indices' device"));
+      if (t.dim() < 1 || t.size(0) != n_src)
+        throw py::value_error(str_cat("take_rows: column ", c, " has ", t.dim() < 1 ? 0 : t.size(0),
+                                      " rows, column 0 has ", n_src));
+      src.push_back(t.contiguous());
+    }
+    c10::hip::HIPGuard guard(idx0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(idx0.device().index()).stream();
+    at::Tensor idx = idx0.contiguous();
+    k::PackCols ps, pd;
+    ps.n = pd.n = static_cast<int>(src.size());
+    std::vector<at::Tensor> outs;
+    for (size_t c = 0; c < src.size(); ++c) {
+      std::vector<int64_t> shape = src[c].sizes().vec();
+      int64_t cell = 1;
+      for (size_t d = 1; d < shape.size(); ++d) cell *= shape[d];
+      shape[0] = n_out;
+      at::Tensor o = pool_empty(shape, src[c].options());
+      ps.row_bytes[c] = pd.row_bytes[c] = cell * static_cast<int64_t>(src[c].element_size());
+      ps.off[c] = pd.off[c] = 0;
+      ps.ptr[c] = src[c].data_ptr();
+      pd.ptr[c] = o.data_ptr();
+      outs.push_back(o);
+    }
+    if (n_out > 0) k::take_rows(ps, pd, idx.data_ptr<int64_t>(), n_out, n_src, s);
+    return outs;
+  }, py::arg("idx"), py::arg("cols"),
+     "output row j of every device column = its row idx[j] (idx: device int64 [n_out], entries in [0, rows), "
+     "repeats allowed), all columns in one launch");
+  // DataFrame.join on device-resident partitions (kernels/join.hip)
+  m.def("join_tile_rows", [] { return k::join_tile_rows(); }, "output rows per block of join_expand");
+  m.def("join_gather_words", [](const at::Tensor& words0, const at::Tensor& perm0) {
+    if (!words0.is_cuda() || words0.scalar_type() != at::kLong || words0.dim() != 2)
+      throw py::value_error("join_gather_words: device int64 words [W, m] expected");
+    const int64_t W = words0.size(0), mm = words0.size(1);
+    if (W < 1 || W > k::kMaxSortKeys)
+      throw py::value_error(str_cat("join_gather_words: 1..", k::kMaxSortKeys, " words per row, got ", W));
+    if (!perm0.is_cuda() || perm0.device() != words0.device() || perm0.scalar_type() != at::kLong ||
+        perm0.dim() != 1 || perm0.size(0) != mm)
+      throw py::value_error(str_cat("join_gather_words: a device int64 permutation [", mm,
+                                    "] on the words' device expected"));
+    c10::hip::HIPGuard guard(words0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(words0.device().index()).stream();
+    at::Tensor words = words0.contiguous(), perm = perm0.contiguous();
+    at::Tensor out = pool_empty({W, mm}, words.options());
+    k::join_gather_words(words.data_ptr<int64_t>(), static_cast<int>(W), mm, perm.data_ptr<int64_t>(),
+                         out.data_ptr<int64_t>(), s);
+    return out;
+  }, py::arg("words"), py::arg("perm"),
+     "words [W, m] in the order perm (sort_argsort): out[w, j] = words[w, perm[j]]");
+  m.def("join_probe", [](const at::Tensor& left0, const at::Tensor& right0, int mask_mode) {
+    if (!left0.is_cuda() || left0.dim() != 2)
+      throw py::value_error("join_probe: device int64 left words [W, n] expected");
+    if (left0.scalar_type() != at::kLong || right0.scalar_type() != at::kLong)
+      throw py::type_error(str_cat("join_probe: the words must be int64, got ", c10::toString(left0.scalar_type()),
+                                   " and ", c10::toString(right0.scalar_type())));
+    if (!right0.is_cuda() || right0.device() != left0.device() || right0.dim() != 2)
+      throw py::value_error("join_probe: device int64 build words [W, m] on the left words' device expected");
+    const int64_t W = left0.size(0), n = left0.size(1), mm = right0.size(1);
+    if (W < 1 || W > k::kMaxSortKeys)
+      throw py::value_error(str_cat("join_probe: 1..", k::kMaxSortKeys, " words per row, got ", W));
+    if (right0.size(0) != W)
+      throw py::value_error(str_cat("join_probe: ", W, " words per left row, ", right0.size(0), " per build row"));
+    if (mask_mode < 0 || mask_mode > 2)
+      throw py::value_error(str_cat("join_probe: mask 0 (none), 1 (matched) or 2 (unmatched) expected, got ", mask_mode));
+    c10::hip::HIPGuard guard(left0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(left0.device().index()).stream();
+    at::Tensor left = left0.contiguous(), right = right0.contiguous();
+    at::Tensor lo = pool_empty({n}, left.options()), cnt = pool_empty({n}, left.options());
+    py::object mask = py::none();
+    uint8_t* mp = nullptr;
+    if (mask_mode != 0) {
+      at::Tensor mt = pool_empty({n}, left.options().dtype(at::kBool));
+      mp = static_cast<uint8_t*>(mt.data_ptr());
+      mask = py::cast(mt);
+    }
+    k::join_probe(left.data_ptr<int64_t>(), static_cast<int>(W), n, mm ? right.data_ptr<int64_t>() : nullptr, mm,
+                  lo.data_ptr<int64_t>(), cnt.data_ptr<int64_t>(), mp, mask_mode, s);
+    return py::make_tuple(lo, cnt, mask);
+  }, py::arg("left"), py::arg("right_sorted"), py::arg("mask") = 0,
+     "left words [W, n] against the build side's words in sorted order [W, m] -> (lo [n]: sorted positions below "
+     "the row's tuple, cnt [n]: positions equal to it, bool mask [n] or None: cnt != 0 for mask=1, cnt == 0 for "
+     "mask=2)");
+  m.def("join_expand", [](const at::Tensor& lo0, const at::Tensor& cnt0, const at::Tensor& perm0) {
+    if (lo0.scalar_type() != at::kLong || cnt0.scalar_type() != at::kLong || perm0.scalar_type() != at::kLong)
+      throw py::type_error("join_expand: int64 lo, cnt and perm expected");
+    if (!lo0.is_cuda() || !cnt0.is_cuda() || !perm0.is_cuda() || cnt0.device() != lo0.device() ||
+        perm0.device() != lo0.device())
+      throw py::value_error("join_expand: lo, cnt and perm must be tensors on one device");
+    if (lo0.dim() != 1 || cnt0.dim() != 1 || perm0.dim() != 1 || cnt0.size(0) != lo0.size(0))
+      throw py::value_error("join_expand: lo [n], cnt [n] and perm [m] expected");
+    const int64_t n = lo0.size(0), mm = perm0.size(0);
+    c10::hip::HIPGuard guard(lo0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(lo0.device().index()).stream();
+    at::Tensor lo = lo0.contiguous(), cnt = cnt0.contiguous(), perm = perm0.contiguous();
+    at::Tensor offs = pool_empty({n + 1}, lo.options());
+    int64_t total = 0;
+    {
+      const size_t wsb = k::join_scan_workspace_bytes(n);
+      at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, lo.options());
+      py::gil_scoped_release nogil;
+      total = k::join_scan(cnt.data_ptr<int64_t>(), n, mm, offs.data_ptr<int64_t>(), ws.data_ptr(),
+                           static_cast<size_t>(ws.numel()) * 8, s);
+    }
+    at::Tensor li = pool_empty({total}, lo.options()), ri = pool_empty({total}, lo.options());
+    k::join_expand(offs.data_ptr<int64_t>(), lo.data_ptr<int64_t>(), perm.data_ptr<int64_t>(), n, mm, total,
+                   li.data_ptr<int64_t>(), ri.data_ptr<int64_t>(), s);
+    return py::make_tuple(li, ri, offs);
+  }, py::arg("lo"), py::arg("cnt"), py::arg("perm"),
+     "join_probe's lo / cnt [n] and the build side's permutation [m] -> (left_idx [total], right_idx [total], offs "
+     "[n + 1]): the exclusive scan of cnt, and per output row the left row and the matching build row, left rows in "
+     "order, a row's matches in sorted (= build row) order; one stream synchronisation reads the total");
   // native JPEG decode into one ragged (pinned) buffer (runtime/jpeg_decode.cpp)
   struct PyJpegBatch {
     std::vector<py::buffer_info> views;  // keep the cells' buffers exported while decoding

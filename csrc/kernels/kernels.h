@@ -193,10 +193,40 @@ int sort_argsort(const int64_t* words, int W, int64_t n, int64_t* perm, void* wo
 // dst.ptr[c] row j = src.ptr[c] row perm[j] for every column (rows of
 // row_bytes[c] bytes, `off` ignored); perm values must lie in [0, n)
 void permute_rows(const PackCols& src, const PackCols& dst, const int64_t* perm, int64_t n, hipStream_t s);
+// the same gather with its own source row count: dst.ptr[c] row j (j < n_out)
+// = src.ptr[c] row idx[j]; indices may repeat and must lie in [0, n_src)
+void take_rows(const PackCols& src, const PackCols& dst, const int64_t* idx, int64_t n_out, int64_t n_src,
+               hipStream_t s);
 // out[i] = rows of the sorted order (perm) whose word tuple is < splitters[i]
 // ([S][W], row-major), lexicographically as unsigned words
 void sort_bounds(const int64_t* words, int W, int64_t n, const int64_t* perm, const int64_t* splitters, int64_t S,
                  int64_t* out, hipStream_t s);
+
+// ------------------------------------------------------------ join (join.hip)
+// DataFrame.join: an equi-join of two frames on key tuples. Keys are the words
+// of sort_encode (ascending), so equal words are Spark's key equality (NaN
+// joins NaN, -0.0 joins 0.0). The build (right) side is sorted with
+// sort_argsort and its words gathered into that order once:
+// out[w][j] = words[w][perm[j]] (words, out: [W][m])
+void join_gather_words(const int64_t* words, int W, int64_t m, const int64_t* perm, int64_t* out, hipStream_t s);
+// per left row i (left: words [W][n]; right_sorted: [W][m], ascending tuples):
+// lo[i] = sorted positions whose tuple is below row i's, cnt[i] = positions
+// whose tuple equals it (they start at lo[i]); m == 0 gives zeros. mask_mode 1
+// also writes mask[i] = (cnt[i] != 0), 2 writes mask[i] = (cnt[i] == 0), 0
+// leaves mask alone
+void join_probe(const int64_t* left, int W, int64_t n, const int64_t* right_sorted, int64_t m, int64_t* lo,
+                int64_t* cnt, uint8_t* mask, int mask_mode, hipStream_t s);
+// offs [n + 1] = exclusive scan of cnt [n] (offs[n] = the total, returned:
+// the stream is synchronised once to read it); m bounds the counts
+size_t join_scan_workspace_bytes(int64_t n);
+int64_t join_scan(const int64_t* cnt, int64_t n, int64_t m, int64_t* offs, void* workspace, size_t workspace_size,
+                  hipStream_t s);
+// for every output row j in [0, total), with i the left row that has
+// offs[i] <= j < offs[i + 1]: left_idx[j] = i, right_idx[j] =
+// perm[lo[i] + (j - offs[i])]. A block owns join_tile_rows() output rows
+int join_tile_rows();
+void join_expand(const int64_t* offs, const int64_t* lo, const int64_t* perm, int64_t n, int64_t m, int64_t total,
+                 int64_t* left_idx, int64_t* right_idx, hipStream_t s);
 
 // ------------------------------------------------------------ data movement
 // dst[idx] = src[idx] over `dims`, both operands addressed by element strides

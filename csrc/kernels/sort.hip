@@ -17,7 +17,9 @@
 //            lanes next to each other cover one row with consecutive pieces, so
 //            stores are fully coalesced and loads are coalesced inside a row
 //            (random only from row to row, which narrow rows cannot avoid).
-//            kUnroll independent loads are in flight per lane;
+//            kUnroll independent loads are in flight per lane. take_rows is
+//            the same kernel with a source row count of its own (any index
+//            list: fewer or more output rows than source rows, repeats);
 //   bounds   lower bounds of splitter tuples in the sorted order (one thread
 //            per splitter, binary search through perm).
 //
@@ -187,16 +189,18 @@ __device__ __forceinline__ void permute_tile(const char* __restrict__ sp, char* 
 
 }  // namespace
 
-// block b: output rows [b * tile, min(n, (b + 1) * tile)) of every column
+// block b: output rows [b * tile, min(n, (b + 1) * tile)) of every column; the
+// source columns hold n_src rows
 __global__ __launch_bounds__(kST) void permute_rows_kernel(PackCols src, PackCols dst, PermuteMeta meta,
-                                                           const int64_t* __restrict__ perm, int64_t n, int tile) {
+                                                           const int64_t* __restrict__ perm, int64_t n, int64_t n_src,
+                                                           int tile) {
   __shared__ uint32_t rows[kPermTile];
   const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * tile;
   const int count = (int)(n - row0 < tile ? n - row0 : tile);
   for (int i = tid; i < count; i += kST) {
     const int64_t p = perm[row0 + i];
-    rows[i] = (uint64_t)p < (uint64_t)n ? (uint32_t)p : 0u;  // never read outside the column
+    rows[i] = (uint64_t)p < (uint64_t)n_src ? (uint32_t)p : 0u;  // never read outside the column
   }
   __syncthreads();
   for (int c = 0; c < src.n; ++c) {
@@ -342,27 +346,33 @@ int sort_argsort(const int64_t* words, int W, int64_t n, int64_t* perm, void* ws
   return passes;
 }
 
-void permute_rows(const PackCols& src, const PackCols& dst, const int64_t* perm, int64_t n, hipStream_t s) {
-  TFA_CHECK(src.n >= 1 && src.n <= kMaxPackCols && dst.n == src.n, "permute_rows: 1..", kMaxPackCols, " columns");
-  TFA_CHECK(n >= 0 && n < (int64_t(1) << 32) - 1, "permute_rows: 0..2^32-2 rows, got ", n);
+namespace {
+
+// dst row j = src row idx[j] for j < n; the source columns hold n_src rows
+void gather_rows_impl(const char* what, const PackCols& src, const PackCols& dst, const int64_t* perm, int64_t n,
+                      int64_t n_src, hipStream_t s) {
+  TFA_CHECK(src.n >= 1 && src.n <= kMaxPackCols && dst.n == src.n, what, ": 1..", kMaxPackCols, " columns");
+  TFA_CHECK(n >= 0 && n < (int64_t(1) << 32) - 1, what, ": 0..2^32-2 rows, got ", n);
+  TFA_CHECK(n_src >= 0 && n_src < (int64_t(1) << 32) - 1, what, ": 0..2^32-2 source rows, got ", n_src);
   if (n == 0) return;
-  TFA_CHECK(perm != nullptr && reinterpret_cast<uintptr_t>(perm) % 8 == 0, "permute_rows: bad permutation buffer");
+  TFA_CHECK(n_src > 0, what, ": rows asked of columns without rows");
+  TFA_CHECK(perm != nullptr && reinterpret_cast<uintptr_t>(perm) % 8 == 0, what, ": bad index buffer");
   int64_t total = 0, widest = 0;
   for (int c = 0; c < src.n; ++c) {
     const int64_t rb = src.row_bytes[c];
-    TFA_CHECK(rb >= 0 && rb == dst.row_bytes[c], "permute_rows: column ", c, " row sizes differ or are negative");
-    TFA_CHECK(rb == 0 || (src.ptr[c] != nullptr && dst.ptr[c] != nullptr), "permute_rows: column ", c, " has no data");
-    TFA_CHECK(rb == 0 || src.ptr[c] != dst.ptr[c], "permute_rows: column ", c, " cannot be permuted in place");
+    TFA_CHECK(rb >= 0 && rb == dst.row_bytes[c], what, ": column ", c, " row sizes differ or are negative");
+    TFA_CHECK(rb == 0 || (src.ptr[c] != nullptr && dst.ptr[c] != nullptr), what, ": column ", c, " has no data");
+    TFA_CHECK(rb == 0 || src.ptr[c] != dst.ptr[c], what, ": column ", c, " cannot be gathered in place");
     total += rb;
     widest = std::max(widest, rb);
   }
   if (total == 0) return;
   // rows per block: about kPermTileBytes of output, and 32-bit offsets inside it
-  TFA_CHECK(widest < (int64_t(1) << 31), "permute_rows: rows of 2 GiB or more");
+  TFA_CHECK(widest < (int64_t(1) << 31), what, ": rows of 2 GiB or more");
   int64_t tile = std::max<int64_t>(1, std::min<int64_t>(kPermTile, kPermTileBytes / total));
   tile = std::min(tile, std::max<int64_t>(1, ((int64_t(1) << 31) - 1) / widest));
   const int64_t blocks = (n + tile - 1) / tile;
-  TFA_CHECK(blocks < (int64_t(1) << 31), "permute_rows: too many blocks");
+  TFA_CHECK(blocks < (int64_t(1) << 31), what, ": too many blocks");
   PermuteMeta meta;
   for (int c = 0; c < kMaxPackCols; ++c) {
     meta.width[c] = 0;
@@ -378,9 +388,20 @@ void permute_rows(const PackCols& src, const PackCols& dst, const int64_t* perm,
     meta.width[c] = width;
     meta.upr[c] = make_fastdiv(static_cast<uint32_t>(rb / width));
   }
-  hipLaunchKernelGGL(permute_rows_kernel, dim3((unsigned)blocks), dim3(kST), 0, s, src, dst, meta, perm, n,
+  hipLaunchKernelGGL(permute_rows_kernel, dim3((unsigned)blocks), dim3(kST), 0, s, src, dst, meta, perm, n, n_src,
                      (int)tile);
   TFA_LAUNCH_CHECK("permute_rows_kernel");
+}
+
+}  // namespace
+
+void permute_rows(const PackCols& src, const PackCols& dst, const int64_t* perm, int64_t n, hipStream_t s) {
+  gather_rows_impl("permute_rows", src, dst, perm, n, n, s);
+}
+
+void take_rows(const PackCols& src, const PackCols& dst, const int64_t* idx, int64_t n_out, int64_t n_src,
+               hipStream_t s) {
+  gather_rows_impl("take_rows", src, dst, idx, n_out, n_src, s);
 }
 
 void sort_bounds(const int64_t* words, int W, int64_t n, const int64_t* perm, const int64_t* splitters, int64_t S,

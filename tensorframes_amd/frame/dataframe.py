@@ -536,6 +536,23 @@ class DataFrame:
     sort = orderBy
     order_by = orderBy
 
+    def join(self, other: "DataFrame", on, how: str = "inner") -> "DataFrame":
+        """Equi-join with `other` on the key column(s) `on` (a name or a list
+        of up to 8 names that both frames hold, with the same type on both
+        sides). `how`: "inner" (the keys, this frame's other columns, then
+        `other`'s), "left_semi" / "semi" (this frame's rows that have a
+        match) or "left_anti" / "anti" (those that have none). Keys compare
+        as in `orderBy`: NaN equals NaN, -0.0 equals 0.0.
+
+        A broadcast join: `other` is gathered whole on every rank, so it
+        should be the small side. The result has this frame's partitions;
+        partition p holds the matches of this frame's partition p in row
+        order, a row's matches in `other`'s global row order -- the same for
+        every world size and every partitioning of `other`. Device-resident
+        partitions are joined on the device (kernels/join.hip)."""
+        from .join import _join_frame
+        return _join_frame(self, other, on, how)
+
     def drop(self, *names) -> "DataFrame":
         return self.select([n for n in self.columns if n not in names])
 

@@ -309,6 +309,125 @@ def _agreed_devices(local: Dict[int, Any], names: Sequence[str]) -> Dict[str, to
     return out
 
 
+def _all_gather_rows(x: torch.Tensor, rows_of_rank: List[int]) -> List[torch.Tensor]:
+    """Every rank's row block of x (rows_of_rank known everywhere), in rank
+    order, on every rank. Host tensors go through `dist.gather_rows`; a
+    device tensor stays on the device: one all-to-all in which every rank
+    sends its block to each rank (RCCL)."""
+    if not x.is_cuda:
+        return dist.gather_rows(x, rows_of_rank, None)
+    from .. import engine
+    w, me = dist.world_size(), dist.rank()
+    got = dist.all_to_all_rows(engine.cat_rows([x] * w), [rows_of_rank[me]] * w, rows_of_rank)
+    out, a = [], 0
+    for r in rows_of_rank:
+        out.append(got[a:a + r])
+        a += r
+    return out
+
+
+def broadcast_frame(local: Dict[int, Any], names: Sequence[str], schema, nparts: int):
+    """ALL rows of the named columns, in global row order (partition order,
+    then row order), as one Block on every rank: the build side of a
+    broadcast join. Collective: every rank calls it with the partitions it
+    owns (p % world), also when it owns none. Dense columns that every rank
+    holds on the device travel as device tensors and stay there (RCCL),
+    other dense columns as host tensors; strings go as lengths plus bytes;
+    anything else is pickled. Each rank's rows arrive as one block per rank,
+    which is cut back into partitions and put into partition order."""
+    from ..frame.block import (Block, StringColumn, build_column, column_tf_dtype, column_values, concat_columns)
+    from ..frame.types import BinaryType
+    from ..ops import groupby as G
+    from .. import engine
+    pids = sorted(local)
+    blocks = [local[p] for p in pids]
+    full = [b for b in blocks if b.nrows]
+    kinds = column_kinds(blocks, names, schema)
+
+    def strings_of(cols, binary):
+        cs = [G.as_string_column(c, binary) for c in cols]
+        if not cs:
+            return _empty_strings(binary)
+        devs = {c.device for c in cs}
+        cat = concat_columns(cs)
+        return cat.to(devs.pop()) if len(devs) == 1 else cat
+
+    if not dist.is_distributed():
+        cols: Dict[str, Any] = {}
+        for n in names:
+            src = [b.columns[n] for b in full]
+            if kinds[n] is not None and src:
+                one = len({c.device for c in src}) == 1
+                cols[n] = engine.cat_rows(src if one else [c.cpu() for c in src])
+            elif is_bytes_field(schema[n]) and all(isinstance(c, (StringColumn,)) for c in src):
+                cols[n] = strings_of(src, isinstance(schema[n].dataType, BinaryType))
+            else:
+                cols[n] = concat_columns([b.columns[n] for b in blocks])
+        return Block(sum(b.nrows for b in blocks), cols)
+
+    w = dist.world_size()
+    counts = partition_rows({p: local[p].nrows for p in pids}, nparts)
+    owned = [[p for p in range(nparts) if p % w == r] for r in range(w)]
+    rows_of_rank = [sum(counts[p] for p in owned[r]) for r in range(w)]
+    # where partition p's rows start in rank r's block
+    start: Dict[int, Tuple[int, int]] = {}
+    for r in range(w):
+        a = 0
+        for p in owned[r]:
+            start[p] = (r, a)
+            a += counts[p]
+    order = [p for p in range(nparts) if counts[p]]
+    devs = _agreed_devices(local, [n for n in names if kinds[n] is not None])
+    # string columns travel through the host; they go back to the device when
+    # every rank that holds rows of them holds them there (the same agreement)
+    snames = [n for n in names if kinds[n] is None and is_bytes_field(schema[n])]
+    sdev = {}
+    if snames:
+        flags = []
+        for n in snames:
+            srcs = [b.columns[n] for b in full]
+            flags.append([int(all(getattr(c, "is_cuda", False) for c in srcs)), -int(bool(srcs))])
+        t = torch.tensor(flags, dtype=torch.int64).reshape(-1)
+        dist.all_reduce_host_(t, "Min")
+        t = t.reshape(len(snames), 2)
+        for i, n in enumerate(snames):
+            on_gpu = engine.gpu_available() and bool(t[i, 0]) and int(t[i, 1]) < 0
+            sdev[n] = engine.compute_device() if on_gpu else torch.device("cpu")
+    cols = {}
+    for n in names:
+        kind = kinds[n]
+        if kind is not None:
+            dev = devs[n]
+            src = [b.columns[n].to(dev) for b in full]
+            mine = engine.cat_rows(src) if src else engine.device_empty((0,) + kind[1], kind[0], dev)
+            got = _all_gather_rows(mine.contiguous(), rows_of_rank)
+            parts = [got[start[p][0]][start[p][1]:start[p][1] + counts[p]] for p in order]
+            cols[n] = engine.cat_rows(parts) if parts else engine.device_empty((0,) + kind[1], kind[0], dev)
+        elif is_bytes_field(schema[n]):
+            binary = isinstance(schema[n].dataType, BinaryType)
+            cat = strings_of([b.columns[n] for b in full], binary).to(torch.device("cpu"))
+            nb = torch.zeros(w, dtype=torch.int64)
+            nb[dist.rank()] = int(cat.data.numel())
+            dist.all_reduce_host_(nb, "Sum")
+            lens = dist.gather_rows(cat.lengths().contiguous(), rows_of_rank, None)
+            data = dist.gather_rows(cat.data.contiguous(), nb.tolist(), None)
+            per_rank = []
+            for r in range(w):
+                offs = torch.zeros(lens[r].shape[0] + 1, dtype=torch.int64)
+                torch.cumsum(lens[r], 0, out=offs[1:])
+                per_rank.append(StringColumn(offs, data[r], binary))
+            parts = [per_rank[start[p][0]].slice(start[p][1], start[p][1] + counts[p]) for p in order]
+            cols[n] = (concat_columns(parts) if parts else _empty_strings(binary)).to(sdev[n])
+        else:
+            tfd = _schema_tf(schema[n])
+            if tfd is None:
+                tfd = next((column_tf_dtype(b.columns[n]) for b in blocks), None)
+            got = dist.all_gather_object([(p, column_values(local[p].columns[n])) for p in pids if local[p].nrows])
+            byp = {p: v for chunk in got for p, v in chunk}
+            cols[n] = build_column([v for p in order for v in byp[p]], tfd)
+    return Block(sum(counts), cols)
+
+
 def repartition_blocks(local: Dict[int, Any], names: Sequence[str], schema, nparts_in: int,
                        nparts_out: int) -> Dict[int, Any]:
     """Rows re-sliced into nparts_out even partitions (in row order); each
