@@ -952,6 +952,85 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "join_probe's lo / cnt [n] and the build side's permutation [m] -> (left_idx [total], right_idx [total], offs "
      "[n + 1]): the exclusive scan of cnt, and per output row the left row and the matching build row, left rows in "
      "order, a row's matches in sorted (= build row) order; one stream synchronisation reads the total");
+  // DataFrame.describe / summary / approxQuantile on device-resident columns (kernels/stats.hip)
+  m.def("stats_tile_rows", [] { return k::stats_tile_rows(); }, "rows per tile of select_hist");
+  // a dense scalar column of one of the seven statistics dtypes, or the typed error
+  auto stat_column = [](const char* what, const at::Tensor& t, const std::string& which) {
+    if (!t.is_cuda()) throw py::value_error(str_cat(what, ": ", which, " must be a device tensor"));
+    if (t.dim() != 1) throw py::value_error(str_cat(what, ": ", which, " must be 1-D (one scalar per row)"));
+    const auto st = t.scalar_type();
+    if (st != at::kFloat && st != at::kDouble && st != at::kLong && st != at::kInt && st != at::kShort &&
+        st != at::kChar && st != at::kByte)
+      throw py::type_error(str_cat(what, ": ", which, " is ", c10::toString(st), ", which is not supported (uint8, "
+                                   "int8, int16, int32, int64, float32 or float64)"));
+    if (!t.is_contiguous())
+      throw py::value_error(str_cat(what, ": ", which, " is not contiguous; make it contiguous first"));
+  };
+  m.def("column_moments", [stat_column](const std::vector<at::Tensor>& cols) {
+    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("column_moments: 1..", k::kMaxPackCols, " columns per call, got ", cols.size()));
+    k::StatCols sc;
+    sc.n = static_cast<int>(cols.size());
+    for (size_t c = 0; c < cols.size(); ++c) {
+      const at::Tensor& t = cols[c];
+      stat_column("column_moments", t, str_cat("column ", c));
+      if (t.device() != cols[0].device())
+        throw py::value_error(str_cat("column_moments: column ", c, " is not on the first column's device"));
+      if (t.size(0) != cols[0].size(0))
+        throw py::value_error(str_cat("column_moments: column ", c, " has ", t.size(0), " rows, the first column ",
+                                      cols[0].size(0)));
+      sc.dtype[c] = from_scalar_type(t.scalar_type());
+      sc.ptr[c] = t.data_ptr();
+    }
+    const int64_t n = cols[0].size(0), C = sc.n;
+    const auto dev = cols[0].device();
+    if (n == 0) {  // nothing is launched
+      at::Tensor mo = at::empty({C, 3}, at::kDouble), ex = at::empty({C, 2}, at::kLong);
+      for (int64_t c = 0; c < C; ++c) {
+        mo.data_ptr<double>()[3 * c] = 0.0;
+        mo.data_ptr<double>()[3 * c + 1] = mo.data_ptr<double>()[3 * c + 2] = std::numeric_limits<double>::quiet_NaN();
+        ex.data_ptr<int64_t>()[2 * c] = -1;  // (all ones)
+        ex.data_ptr<int64_t>()[2 * c + 1] = 0;
+      }
+      return py::make_tuple(mo.to(dev), ex.to(dev));
+    }
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    at::Tensor mo = pool_empty({C, 3}, cols[0].options().dtype(at::kDouble));
+    at::Tensor ex = pool_empty({C, 2}, cols[0].options().dtype(at::kLong));
+    const size_t wsb = k::column_moments_workspace_bytes(sc.n, n);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, cols[0].options().dtype(at::kLong));
+    k::column_moments(sc, n, mo.data_ptr<double>(), ex.data_ptr<int64_t>(), ws.data_ptr(),
+                      static_cast<size_t>(ws.numel()) * 8, s);
+    return py::make_tuple(mo, ex);
+  }, py::arg("cols"),
+     "up to 16 dense scalar device columns [n] (mixed dtypes, contiguous) -> (moments f64 [C, 3]: n, mean, M2 = the "
+     "sum of squared deviations; extremes int64 [C, 2]: the smallest and largest order-preserving word, bit "
+     "patterns), device tensors; the same bits on every run. n == 0 gives (0, NaN, NaN) and (all ones, 0)");
+  m.def("select_hist", [stat_column](const at::Tensor& col, const at::Tensor& prefixes0, int prefix_bits) {
+    stat_column("select_hist", col, "the column");
+    if (prefixes0.scalar_type() != at::kLong || prefixes0.dim() != 1)
+      throw py::value_error("select_hist: int64 prefixes [P] expected");
+    const int64_t P = prefixes0.size(0);
+    if (P < 1 || P > k::kMaxPackCols)
+      throw py::value_error(str_cat("select_hist: 1..", k::kMaxPackCols, " prefixes per call, got ", P));
+    if (prefix_bits < 0 || prefix_bits > 56 || prefix_bits % 8 != 0)
+      throw py::value_error(str_cat("select_hist: prefix_bits must be one of 0, 8, ..., 56, got ", prefix_bits));
+    if (prefix_bits == 0 && P != 1)
+      throw py::value_error(str_cat("select_hist: without a prefix (prefix_bits 0) there is one histogram, got ", P,
+                                    " prefixes"));
+    // (the prefixes travel as kernel arguments: a device tensor is read back first)
+    at::Tensor prefixes = prefixes0.cpu().contiguous();
+    c10::hip::HIPGuard guard(col.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(col.device().index()).stream();
+    at::Tensor hist = pool_empty({P, 256}, col.options().dtype(at::kLong));
+    k::select_hist(from_scalar_type(col.scalar_type()), col.data_ptr(), col.size(0), prefixes.data_ptr<int64_t>(),
+                   static_cast<int>(P), prefix_bits, hist.data_ptr<int64_t>(), s);
+    return hist;
+  }, py::arg("col"), py::arg("prefixes"), py::arg("prefix_bits"),
+     "one step of a radix select over a dense scalar device column: int64 [P, 256], hist[p][d] = rows whose "
+     "order-preserving word has its top prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] and whose "
+     "next 8-bit digit is d; exact counts");
   // native JPEG decode into one ragged (pinned) buffer (runtime/jpeg_decode.cpp)
   struct PyJpegBatch {
     std::vector<py::buffer_info> views;  // keep the cells' buffers exported while decoding

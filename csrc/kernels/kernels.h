@@ -228,6 +228,37 @@ int join_tile_rows();
 void join_expand(const int64_t* offs, const int64_t* lo, const int64_t* perm, int64_t n, int64_t m, int64_t total,
                  int64_t* left_idx, int64_t* right_idx, hipStream_t s);
 
+// ------------------------------------------------------------ stats (stats.hip)
+// DataFrame.describe / summary / approxQuantile on device-resident columns.
+// Columns are dense scalar columns [n] of uint8, int8, int16, int32, int64,
+// float32 or float64 (mixed), read where they are: 16-byte vector loads from
+// the first aligned element on, a scalar head and tail around them.
+struct StatCols {
+  int n = 0;
+  DType dtype[kMaxPackCols];
+  const void* ptr[kMaxPackCols];  // [rows] each, contiguous, aligned to the element
+};
+// one record per column in one launch pair: moments[c] = {n, mean, M2 (the sum
+// of squared deviations from the mean)} as f64, every element converted to f64
+// first; extremes[c] = {smallest, largest} order-preserving word of the column
+// (the ascending table of the sort section). Welford per lane, Chan's merge
+// across lanes, waves and (through per-block partial records and a one-block
+// fold in block order) blocks: no float atomics, the same bits on every run.
+// n == 0 launches nothing and leaves the outputs alone (the caller fills
+// {0, NaN, NaN} and {all ones, 0}).
+size_t column_moments_workspace_bytes(int ncols, int64_t n);
+void column_moments(const StatCols& cols, int64_t n, double* moments, int64_t* extremes, void* workspace,
+                    size_t workspace_size, hipStream_t s);
+// hist[p][d] (device int64 [P][256], overwritten) = rows whose word has its top
+// prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] (host) and whose
+// next 8-bit digit is d; prefix_bits == 0 takes P == 1 and ignores the prefix.
+// The word is computed from the raw column on the fly. 1 <= P <= kMaxPackCols.
+// Per-wave LDS histograms, folded per block, added with 64-bit integer
+// atomics: exact counts. A block reads tiles of stats_tile_rows() rows.
+int stats_tile_rows();  // radix::kTile
+void select_hist(DType dtype, const void* col, int64_t n, const int64_t* prefixes, int P, int prefix_bits,
+                 int64_t* hist, hipStream_t s);
+
 // ------------------------------------------------------------ data movement
 // dst[idx] = src[idx] over `dims`, both operands addressed by element strides
 // (src strides may be 0 or negative; pointers already include the offsets).

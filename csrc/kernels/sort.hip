@@ -29,6 +29,7 @@
 
 #include "hip_common.h"
 #include "radix.h"
+#include "sort_words.h"
 
 namespace tfa {
 namespace k {
@@ -39,27 +40,9 @@ constexpr int kST = 256;            // threads per block of every kernel here
 constexpr int kPermTile = 2048;     // most output rows per permute block
 constexpr int64_t kPermTileBytes = 64 << 10;  // output bytes per permute block to aim for
 constexpr int kUnroll = 4;          // loads in flight per lane
-constexpr uint64_t kSign64 = 0x8000000000000000ull;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint64_t encode_f32(uint32_t b) {
-  if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;  // every NaN: the canonical quiet NaN
-  if (b == 0x80000000u) b = 0u;                          // -0.0 == +0.0
-  return (b & 0x80000000u) ? static_cast<uint32_t>(~b) : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ uint64_t encode_f64(uint64_t b) {
-  if ((b & ~kSign64) > 0x7ff0000000000000ull) b = 0x7ff8000000000000ull;
-  if (b == kSign64) b = 0ull;
-  return (b & kSign64) ? ~b : (b | kSign64);
-}
-
-template <typename T>
-__device__ __forceinline__ uint64_t encode_int(T v) {
-  return static_cast<uint64_t>(static_cast<int64_t>(v)) ^ kSign64;
-}
 
 // one key column: rows grid-stride; `flip` is the descending complement
 template <typename T, typename F>

@@ -553,6 +553,50 @@ class DataFrame:
         from .join import _join_frame
         return _join_frame(self, other, on, how)
 
+    def describe(self, *cols) -> "DataFrame":
+        """count, mean, stddev, min and max of the named columns, or of every
+        numeric scalar column (uint8, int8, int16, int32, int64, float,
+        double; the others are skipped) when none is named: a one-partition
+        frame with a string column `summary` (the row labels) and one DOUBLE
+        column per described column (Spark returns strings). An action, and
+        collective: every rank calls it. `stddev` is the sample standard
+        deviation (NaN below two rows); `min` / `max` follow `orderBy`'s
+        order (NaN after +inf). Device-resident columns are read once by the
+        moments kernel (kernels/stats.hip); for a given partitioning the
+        result has the same bits for every number of ranks."""
+        from .stats import describe
+        return describe(self, *cols)
+
+    def summary(self, *statistics) -> "DataFrame":
+        """`describe` of every numeric scalar column with chosen statistics:
+        any of "count", "mean", "stddev", "min", "max" and percentiles such as
+        "25%" (any number in [0, 100], at most 16); by default count, mean,
+        stddev, min, 25%, 50%, 75%, max. Percentiles are exact
+        (`approxQuantile`)."""
+        from .stats import summary
+        return summary(self, *statistics)
+
+    def approxQuantile(self, col, probabilities, relativeError=0.0):  # noqa: N802, N803
+        """The quantiles of a numeric scalar column at `probabilities` (at
+        most 16 numbers in [0, 1]) as a list of floats, or for a list of
+        columns one such list per column. Quantile p is the row at 0-based
+        position max(ceil(p * N) - 1, 0) of `orderBy(col)` (numpy's
+        `inverted_cdf`); NaNs count as rows and sort last. Every
+        `relativeError` >= 0 returns the exact value: a radix selection over
+        the order-preserving words of the sort path, at most 8 read-only
+        passes over the column (kernels/stats.hip on the device), no row
+        moves. An empty frame gives []. An action, and collective."""
+        from .stats import approx_quantile
+        return approx_quantile(self, col, probabilities, relativeError)
+
+    approx_quantile = approxQuantile
+
+    @property
+    def stat(self):
+        """Spark's `df.stat` accessor (`df.stat.approxQuantile(...)`)."""
+        from .stats import DataFrameStatFunctions
+        return DataFrameStatFunctions(self)
+
     def drop(self, *names) -> "DataFrame":
         return self.select([n for n in self.columns if n not in names])
 
