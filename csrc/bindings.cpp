@@ -1031,6 +1031,139 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "one step of a radix select over a dense scalar device column: int64 [P, 256], hist[p][d] = rows whose "
      "order-preserving word has its top prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] and whose "
      "next 8-bit digit is d; exact counts");
+  // GroupedData.agg / DataFrame.agg on device-resident columns (kernels/group_stats.hip)
+  m.def("group_chunk_rows", [] { return k::group_chunk_rows(); }, "rows per work item of group_moments");
+  // int64 device records [*, C, 6], contiguous
+  auto group_records = [](const char* what, const at::Tensor& t) {
+    if (!t.is_cuda()) throw py::value_error(str_cat(what, ": the records must be a device tensor"));
+    if (t.scalar_type() != at::kLong) throw py::type_error(str_cat(what, ": the records must be int64 bit patterns"));
+    if (t.dim() != 3 || t.size(2) != k::kGroupRecordFields || t.size(1) < 1 || t.size(1) > k::kMaxPackCols)
+      throw py::value_error(str_cat(what, ": records [*, 1..", k::kMaxPackCols, ", ", k::kGroupRecordFields,
+                                    "] expected"));
+    if (!t.is_contiguous()) throw py::value_error(str_cat(what, ": the records are not contiguous"));
+  };
+  auto group_index = [](const char* what, const char* which, const at::Tensor& t, const at::Device& dev) {
+    if (t.scalar_type() != at::kLong) throw py::type_error(str_cat(what, ": ", which, " must be int64"));
+    if (!t.is_cuda() || t.device() != dev)
+      throw py::value_error(str_cat(what, ": ", which, " must be a tensor on the columns' device"));
+    if (t.dim() != 1) throw py::value_error(str_cat(what, ": ", which, " must be 1-D"));
+    if (!t.is_contiguous()) throw py::value_error(str_cat(what, ": ", which, " is not contiguous"));
+  };
+  m.def("group_moments", [stat_column, group_index](const std::vector<at::Tensor>& cols, const at::Tensor& perm,
+                                                    const at::Tensor& offsets) {
+    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("group_moments: 1..", k::kMaxPackCols, " columns per call, got ", cols.size()));
+    k::StatCols sc;
+    sc.n = static_cast<int>(cols.size());
+    for (size_t c = 0; c < cols.size(); ++c) {
+      const at::Tensor& t = cols[c];
+      stat_column("group_moments", t, str_cat("column ", c));
+      if (t.device() != cols[0].device())
+        throw py::value_error(str_cat("group_moments: column ", c, " is not on the first column's device"));
+      if (t.size(0) != cols[0].size(0))
+        throw py::value_error(str_cat("group_moments: column ", c, " has ", t.size(0), " rows, the first column ",
+                                      cols[0].size(0)));
+      sc.dtype[c] = from_scalar_type(t.scalar_type());
+      sc.ptr[c] = t.data_ptr();
+    }
+    const auto dev = cols[0].device();
+    group_index("group_moments", "perm", perm, dev);
+    group_index("group_moments", "offsets", offsets, dev);
+    const int64_t n = cols[0].size(0), C = sc.n;
+    if (perm.size(0) != n)
+      throw py::value_error(str_cat("group_moments: perm has ", perm.size(0), " entries, the columns ", n, " rows"));
+    if (offsets.size(0) < 1) throw py::value_error("group_moments: offsets [nseg + 1] expected, got none");
+    const int64_t nseg = offsets.size(0) - 1;
+    if (n == 0 || nseg == 0) {  // nothing is launched: empty records
+      at::Tensor rec = at::zeros({nseg, C, k::kGroupRecordFields}, at::kLong);
+      if (nseg) rec.select(2, 4).fill_(-1);  // (all ones)
+      return rec.to(dev);
+    }
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    at::Tensor rec = pool_empty({nseg, C, k::kGroupRecordFields}, cols[0].options().dtype(at::kLong));
+    const size_t wsb = k::group_moments_workspace_bytes(sc.n, n, nseg);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, cols[0].options().dtype(at::kLong));
+    {
+      py::gil_scoped_release nogil;
+      k::group_moments(sc, n, perm.data_ptr<int64_t>(), n, offsets.data_ptr<int64_t>(), nseg, rec.data_ptr<int64_t>(),
+                       ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    }
+    return rec;
+  }, py::arg("cols"), py::arg("perm"), py::arg("offsets"),
+     "up to 16 dense scalar device columns [n] (mixed dtypes, contiguous) and segment_csr's (perm [n], offsets "
+     "[nseg + 1]) -> int64 records [nseg, C, 6] (bit patterns): n, mean, M2 as f64, the sum (wrapping int64 for "
+     "integer columns, f64 for float ones), the smallest and largest order-preserving word. A record depends on its "
+     "segment's rows in row order alone; the same bits on every run. One stream synchronisation reads the number of "
+     "work items; n == 0 launches nothing and gives empty records (0, 0, 0, 0, all ones, 0)");
+  m.def("merge_group_records", [group_records, group_index](const at::Tensor& recs, const at::Tensor& offsets,
+                                                            const std::vector<bool>& is_float) {
+    group_records("merge_group_records", recs);
+    group_index("merge_group_records", "offsets", offsets, recs.device());
+    const int64_t mm = recs.size(0), C = recs.size(1);
+    if (static_cast<int64_t>(is_float.size()) != C)
+      throw py::value_error(str_cat("merge_group_records: ", C, " record columns, ", is_float.size(), " float flags"));
+    if (offsets.size(0) < 1) throw py::value_error("merge_group_records: offsets [ng + 1] expected, got none");
+    const int64_t ng = offsets.size(0) - 1;
+    uint32_t mask = 0;
+    for (int64_t c = 0; c < C; ++c) mask |= is_float[c] ? (1u << c) : 0u;
+    c10::hip::HIPGuard guard(recs.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(recs.device().index()).stream();
+    at::Tensor out = pool_empty({ng, C, k::kGroupRecordFields}, recs.options());
+    k::merge_group_records(mm ? recs.data_ptr<int64_t>() : nullptr, mm, static_cast<int>(C), mask,
+                           offsets.data_ptr<int64_t>(), ng, out.data_ptr<int64_t>(), s);
+    return out;
+  }, py::arg("records"), py::arg("offsets"), py::arg("is_float"),
+     "records [m, C, 6] ordered by (key, partition) and CSR offsets [ng + 1] over them -> [ng, C, 6]: each group's "
+     "records merged in order with Chan's formula (integer sums add, float sums add in that order, words take min "
+     "and max); is_float[c]: column c is float32 / float64");
+  m.def("group_results", [group_records](const at::Tensor& recs, const std::vector<int64_t>& cols,
+                                         const std::vector<std::string>& stats,
+                                         const std::vector<at::ScalarType>& dtypes) {
+    static const char* const names[] = {"count", "sum", "avg", "min", "max", "var_samp", "var_pop", "stddev_samp",
+                                        "stddev_pop"};
+    group_records("group_results", recs);
+    const int64_t ng = recs.size(0), C = recs.size(1);
+    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("group_results: 1..", k::kMaxPackCols, " outputs per call, got ", cols.size()));
+    if (stats.size() != cols.size() || dtypes.size() != cols.size())
+      throw py::value_error("group_results: one statistic and one column dtype per output expected");
+    k::GroupResultSpec spec;
+    spec.n = static_cast<int>(cols.size());
+    c10::hip::HIPGuard guard(recs.device().index());
+    std::vector<at::Tensor> outs;
+    for (size_t o = 0; o < cols.size(); ++o) {
+      if (cols[o] < 0 || cols[o] >= C)
+        throw py::value_error(str_cat("group_results: output ", o, " names column ", cols[o], " of ", C));
+      int st = -1;
+      for (int i = 0; i < 9; ++i)
+        if (stats[o] == names[i]) st = i;
+      if (st < 0) throw py::value_error(str_cat("group_results: '", stats[o], "' is not a statistic"));
+      const at::ScalarType ct = dtypes[o];
+      if (ct != at::kFloat && ct != at::kDouble && ct != at::kLong && ct != at::kInt && ct != at::kShort &&
+          ct != at::kChar && ct != at::kByte)
+        throw py::type_error(str_cat("group_results: output ", o, " reads a ", c10::toString(ct), " column, which is "
+                                     "not supported (uint8, int8, int16, int32, int64, float32 or float64)"));
+      const bool fl = ct == at::kFloat || ct == at::kDouble;
+      const auto gs = static_cast<k::GroupStat>(st);
+      at::ScalarType ot = at::kDouble;
+      if (gs == k::GroupStat::COUNT || (gs == k::GroupStat::SUM && !fl)) ot = at::kLong;
+      if (gs == k::GroupStat::MIN || gs == k::GroupStat::MAX) ot = ct;
+      outs.push_back(pool_empty({ng}, recs.options().dtype(ot)));
+      spec.col[o] = static_cast<int>(cols[o]);
+      spec.stat[o] = gs;
+      spec.dtype[o] = from_scalar_type(ct);
+      spec.out[o] = outs.back().data_ptr();
+    }
+    k::group_results(ng ? recs.data_ptr<int64_t>() : nullptr, ng, static_cast<int>(C), spec,
+                     c10::hip::getCurrentHIPStream(recs.device().index()).stream());
+    return outs;
+  }, py::arg("records"), py::arg("cols"), py::arg("stats"), py::arg("dtypes"),
+     "merged records [ng, C, 6] -> one device column [ng] per output (up to 16, one launch): output o is statistic "
+     "stats[o] (count, sum, avg, min, max, var_samp, var_pop, stddev_samp, stddev_pop) of record column cols[o], whose "
+     "values have dtype dtypes[o]. count and integer sums are int64, min / max the column's dtype (words decoded: "
+     "-0.0 comes back as 0.0), the others float64; a NaN or opposite infinities in a float group give NaN, the "
+     "sample statistics NaN below two rows");
   // native JPEG decode into one ragged (pinned) buffer (runtime/jpeg_decode.cpp)
   struct PyJpegBatch {
     std::vector<py::buffer_info> views;  // keep the cells' buffers exported while decoding

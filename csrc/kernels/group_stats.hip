@@ -1,0 +1,469 @@
+// Grouped statistics for GroupedData.agg / DataFrame.agg.
+//
+// A record is six 8-byte fields per (group, value column): n, mean and M2 as
+// f64 (every element converted to f64 first, as in stats.hip), the sum (the
+// int64 bits of a wrapping sum for the integer dtypes, an f64 running sum for
+// the float ones) and the smallest and largest ascending sort word.
+//
+//   group_moments   rows come as CSR segments (perm, offsets) of segment_csr.
+//            The work split is the per-segment chunking: a work item is a
+//            (segment, chunk) pair, a chunk at most kGroupChunk rows of one
+//            segment (every segment has at least one item, an empty one too).
+//            The chunk counts are scanned on the device (join_scan: one stream
+//            synchronisation reads the total); an item finds its segment by a
+//            binary search in the scanned counts. One wave takes one item: the
+//            lanes read the chunk's rows at stride 64 through perm, Welford per
+//            lane, the lanes' records merged with Chan's formula in lane order
+//            (xor butterfly), sums added in the same order. The column is the
+//            grid's y. Segments of more than one chunk are folded in chunk
+//            order by a second kernel: one thread per segment and column up
+//            to kFoldSerial chunks; a longer segment (measured: half of 10M
+//            rows in one key is 9766 chunks, 3.2 ms folded by one thread) is
+//            folded by the thread's wave, each lane a run of consecutive
+//            chunks, the lanes in lane order. When every segment is one chunk
+//            the first kernel writes the result itself. A group's record
+//            depends on its own rows in row order alone: not on the other
+//            groups, not on the run.
+//   merge_group_records   records ordered by (key, partition), CSR offsets
+//            over them: one thread per (group, column) folds its records
+//            sequentially, starting from the first.
+//   group_results   merged records -> typed output columns, up to
+//            kMaxPackCols of them in one launch (the output is the grid's y):
+//            words decoded back to the column's type, the NaN / infinity rule
+//            of describe decided from the extreme words, sqrt(M2 / (n - 1))
+//            and the rest.
+//
+// No float atomics, no inter-block communication, every loop bounded by the
+// row count.
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+#include "hip_common.h"
+#include "sort_words.h"
+
+namespace tfa {
+namespace k {
+
+namespace {
+
+constexpr int kT = 256;  // threads per block of every kernel here
+constexpr int kWaves = kT / kWave;
+constexpr int kGroupChunk = 512;  // rows per work item
+constexpr int kLaneRows = 4;      // independent loads in flight per lane
+constexpr int kFoldSerial = 8;    // most chunks of a segment one thread folds on its own
+
+struct GRec {
+  double n, mean, m2;
+  uint64_t sum, lo, hi;
+};
+static_assert(sizeof(GRec) == 8 * kGroupRecordFields, "a record is six 8-byte fields");
+
+__device__ __forceinline__ GRec grec_empty() { return GRec{0.0, 0.0, 0.0, 0ull, ~0ull, 0ull}; }
+
+__device__ __forceinline__ uint64_t f64_bits(double x) { return static_cast<uint64_t>(__double_as_longlong(x)); }
+__device__ __forceinline__ double bits_f64(uint64_t b) { return __longlong_as_double(static_cast<long long>(b)); }
+
+// Chan's merge of two records, `a` the earlier rows (the arithmetic of
+// stats.hip's rec_merge, plus the sum)
+__device__ __forceinline__ GRec grec_merge(const GRec& a, const GRec& b, bool is_float) {
+  GRec r;
+  r.n = a.n + b.n;
+  const double delta = b.mean - a.mean;
+  const double f = r.n > 0.0 ? b.n / r.n : 0.0;
+  r.mean = a.n == 0.0 ? b.mean : (b.n == 0.0 ? a.mean : a.mean + delta * f);
+  r.m2 = a.n == 0.0 ? b.m2 : (b.n == 0.0 ? a.m2 : a.m2 + b.m2 + delta * delta * (a.n * f));
+  r.sum = is_float ? (a.n == 0.0 ? b.sum : (b.n == 0.0 ? a.sum : f64_bits(bits_f64(a.sum) + bits_f64(b.sum))))
+                   : a.sum + b.sum;
+  r.lo = a.lo < b.lo ? a.lo : b.lo;
+  r.hi = a.hi > b.hi ? a.hi : b.hi;
+  return r;
+}
+
+__device__ __forceinline__ GRec grec_shfl_xor(const GRec& r, int off) {
+  GRec o;
+  o.n = __shfl_xor(r.n, off, kWave);
+  o.mean = __shfl_xor(r.mean, off, kWave);
+  o.m2 = __shfl_xor(r.m2, off, kWave);
+  o.sum = __shfl_xor(static_cast<unsigned long long>(r.sum), off, kWave);
+  o.lo = __shfl_xor(static_cast<unsigned long long>(r.lo), off, kWave);
+  o.hi = __shfl_xor(static_cast<unsigned long long>(r.hi), off, kWave);
+  return o;
+}
+
+__device__ __forceinline__ bool float_dtype(DType d) { return d == DType::F32 || d == DType::F64; }
+
+template <typename T>
+struct SumOf {  // integers: wrapping 64-bit; floats: f64
+  static __device__ __forceinline__ void add(uint64_t& s, double&, T v) {
+    s += static_cast<uint64_t>(static_cast<int64_t>(v));
+  }
+  static __device__ __forceinline__ uint64_t bits(uint64_t s, double) { return s; }
+};
+template <>
+struct SumOf<float> {
+  static __device__ __forceinline__ void add(uint64_t&, double& s, float v) { s += static_cast<double>(v); }
+  static __device__ __forceinline__ uint64_t bits(uint64_t, double s) { return f64_bits(s); }
+};
+template <>
+struct SumOf<double> {
+  static __device__ __forceinline__ void add(uint64_t&, double& s, double v) { s += v; }
+  static __device__ __forceinline__ uint64_t bits(uint64_t, double s) { return f64_bits(s); }
+};
+
+// one lane's record of rows perm[lo + lane], perm[lo + lane + 64], ... below hi
+// (0 <= lo <= hi <= the length of perm); a perm value outside [0, n) is skipped
+template <typename T>
+__device__ __forceinline__ GRec lane_rows(const void* __restrict__ src, const int64_t* __restrict__ perm, int64_t lo,
+                                          int64_t hi, int64_t n, int lane) {
+  const T* __restrict__ p = static_cast<const T*>(src);
+  double cnt = 0.0, mean = 0.0, m2 = 0.0, fsum = 0.0;
+  uint64_t isum = 0, wlo = ~0ull, whi = 0ull;
+  for (int64_t r = lo + lane; r < hi; r += kLaneRows * kWave) {
+    int64_t idx[kLaneRows];
+    T v[kLaneRows];
+#pragma unroll
+    for (int j = 0; j < kLaneRows; ++j) {
+      const int64_t rr = r + j * kWave;
+      idx[j] = rr < hi ? perm[rr] : -1;
+    }
+#pragma unroll
+    for (int j = 0; j < kLaneRows; ++j) v[j] = (idx[j] >= 0 && idx[j] < n) ? p[idx[j]] : T(0);
+#pragma unroll
+    for (int j = 0; j < kLaneRows; ++j) {
+      if (idx[j] >= 0 && idx[j] < n) {
+        const double x = static_cast<double>(v[j]);
+        cnt += 1.0;
+        const double d = x - mean;
+        mean += d / cnt;
+        m2 += d * (x - mean);
+        SumOf<T>::add(isum, fsum, v[j]);
+        const uint64_t w = sort_word(v[j]);
+        wlo = w < wlo ? w : wlo;
+        whi = w > whi ? w : whi;
+      }
+    }
+  }
+  GRec out = grec_empty();
+  if (cnt > 0.0) out = GRec{cnt, mean, m2, SumOf<T>::bits(isum, fsum), wlo, whi};
+  return out;
+}
+
+// the last i in [a, b] with p[i] <= j (p[a] <= j is given)
+__device__ __forceinline__ int64_t last_not_above(const int64_t* __restrict__ p, int64_t a, int64_t b, int64_t j) {
+  while (a < b) {
+    const int64_t mid = a + (b - a + 1) / 2;
+    if (p[mid] <= j) a = mid;
+    else b = mid - 1;
+  }
+  return a;
+}
+
+__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ void store_rec(int64_t* __restrict__ dst, const GRec& r) {
+  dst[0] = static_cast<int64_t>(f64_bits(r.n));
+  dst[1] = static_cast<int64_t>(f64_bits(r.mean));
+  dst[2] = static_cast<int64_t>(f64_bits(r.m2));
+  dst[3] = static_cast<int64_t>(r.sum);
+  dst[4] = static_cast<int64_t>(r.lo);
+  dst[5] = static_cast<int64_t>(r.hi);
+}
+
+__device__ __forceinline__ GRec load_rec(const int64_t* __restrict__ src) {
+  GRec r;
+  r.n = bits_f64(static_cast<uint64_t>(src[0]));
+  r.mean = bits_f64(static_cast<uint64_t>(src[1]));
+  r.m2 = bits_f64(static_cast<uint64_t>(src[2]));
+  r.sum = static_cast<uint64_t>(src[3]);
+  r.lo = static_cast<uint64_t>(src[4]);
+  r.hi = static_cast<uint64_t>(src[5]);
+  return r;
+}
+
+}  // namespace
+
+// cnt[g] = chunks of segment g, at least one
+__global__ __launch_bounds__(kT) void group_chunk_count_kernel(const int64_t* __restrict__ offsets, int64_t nseg,
+                                                               int64_t nperm, int64_t* __restrict__ cnt) {
+  const int64_t g = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (g >= nseg) return;
+  const int64_t a = clamp64(offsets[g], 0, nperm), b = clamp64(offsets[g + 1], a, nperm);
+  const int64_t c = (b - a + kGroupChunk - 1) / kGroupChunk;
+  cnt[g] = c < 1 ? 1 : c;
+}
+
+// wave w of block (b, c): item b * kWaves + w of column c -> part[item][c].
+// coffs [nseg + 1]: the exclusive scan of the chunk counts, coffs[nseg] == items
+__global__ __launch_bounds__(kT) void group_moments_kernel(StatCols cols, int64_t n, const int64_t* __restrict__ perm,
+                                                           int64_t nperm, const int64_t* __restrict__ offsets,
+                                                           const int64_t* __restrict__ coffs, int64_t nseg,
+                                                           int64_t items, int64_t* __restrict__ part) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int c = blockIdx.y;
+  const int64_t item = (int64_t)blockIdx.x * kWaves +
+                       __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x / kWave));
+  if (item >= items) return;  // (the whole wave)
+  // coffs[0] == 0 <= item < coffs[nseg]: the segment lies in [0, nseg - 1]
+  const int64_t g = last_not_above(coffs, 0, nseg - 1, item);
+  const int64_t ch = item - coffs[g];
+  const int64_t a = clamp64(offsets[g], 0, nperm), b = clamp64(offsets[g + 1], a, nperm);
+  const int64_t lo = clamp64(a + ch * kGroupChunk, a, b);
+  const int64_t hi = lo + kGroupChunk < b ? lo + kGroupChunk : b;
+  const void* src = cols.ptr[c];
+  const DType dt = cols.dtype[c];
+  GRec r;
+  switch (dt) {  // (uniform: one scalar branch per block)
+    case DType::F32: r = lane_rows<float>(src, perm, lo, hi, n, lane); break;
+    case DType::F64: r = lane_rows<double>(src, perm, lo, hi, n, lane); break;
+    case DType::I64: r = lane_rows<int64_t>(src, perm, lo, hi, n, lane); break;
+    case DType::I32: r = lane_rows<int32_t>(src, perm, lo, hi, n, lane); break;
+    case DType::I16: r = lane_rows<int16_t>(src, perm, lo, hi, n, lane); break;
+    case DType::I8: r = lane_rows<int8_t>(src, perm, lo, hi, n, lane); break;
+    default: r = lane_rows<uint8_t>(src, perm, lo, hi, n, lane); break;  // U8
+  }
+  const bool fl = float_dtype(dt);
+  const int64_t rows = hi - lo;  // (the same in every lane)
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {  // lane order: neighbours first
+    // lanes from `rows` on hold empty records, and merging an empty record
+    // changes no bit: a short chunk stops early (a one-row group merges nothing)
+    if (off >= rows) break;
+    const GRec o = grec_shfl_xor(r, off);
+    r = (lane & off) ? grec_merge(o, r, fl) : grec_merge(r, o, fl);
+  }
+  if (lane == 0) store_rec(part + (item * gridDim.y + c) * kGroupRecordFields, r);
+}
+
+// thread (g, c): part[coffs[g] .. coffs[g + 1])[c] merged in chunk order -> out[g][c].
+// Up to kFoldSerial chunks: the thread folds them one after the other. More
+// (a key that holds a large share of the rows): the wave takes the thread's
+// pair together, lane l the l-th run of ceil(chunks / 64) consecutive chunks,
+// the lanes' records merged in lane order: still chunk order, and a function
+// of the segment's chunk count alone.
+__global__ __launch_bounds__(kT) void group_fold_kernel(StatCols cols, const int64_t* __restrict__ part,
+                                                        const int64_t* __restrict__ coffs, int64_t nseg, int64_t items,
+                                                        int64_t* __restrict__ out) {
+  const int C = cols.n;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t t = (int64_t)blockIdx.x * kT + threadIdx.x;
+  const bool valid = t < nseg * C;
+  const int64_t g = valid ? t / C : 0;
+  const int c = valid ? static_cast<int>(t - g * C) : 0;
+  const int64_t a = clamp64(coffs[g], 0, items - 1), b = clamp64(coffs[g + 1], a + 1, items);
+  const bool wide = valid && b - a > kFoldSerial;
+  if (valid && !wide) {
+    const bool fl = float_dtype(cols.dtype[c]);
+    GRec r = load_rec(part + (a * C + c) * kGroupRecordFields);
+    for (int64_t i = a + 1; i < b; ++i) r = grec_merge(r, load_rec(part + (i * C + c) * kGroupRecordFields), fl);
+    store_rec(out + t * kGroupRecordFields, r);
+  }
+  unsigned long long todo = __ballot(wide);  // (the same in every lane: at most 64 rounds)
+  while (todo) {
+    const int src = __ffsll(todo) - 1;
+    todo &= todo - 1;
+    const int64_t sa = __shfl(static_cast<long long>(a), src, kWave), sb = __shfl(static_cast<long long>(b), src, kWave);
+    const int64_t st = __shfl(static_cast<long long>(t), src, kWave);
+    const int sc = __shfl(c, src, kWave);
+    const bool fl = float_dtype(cols.dtype[sc]);
+    const int64_t per = (sb - sa + kWave - 1) / kWave;
+    const int64_t i0 = sa + lane * per < sb ? sa + lane * per : sb, i1 = i0 + per < sb ? i0 + per : sb;
+    GRec r = grec_empty();
+    if (i0 < i1) r = load_rec(part + (i0 * C + sc) * kGroupRecordFields);
+    for (int64_t i = i0 + 1; i < i1; ++i) r = grec_merge(r, load_rec(part + (i * C + sc) * kGroupRecordFields), fl);
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+      const GRec o = grec_shfl_xor(r, off);
+      r = (lane & off) ? grec_merge(o, r, fl) : grec_merge(r, o, fl);
+    }
+    if (lane == 0) store_rec(out + st * kGroupRecordFields, r);
+  }
+}
+
+// thread (g, c): recs[offsets[g] .. offsets[g + 1])[c] merged in order -> out[g][c]
+__global__ __launch_bounds__(kT) void merge_group_records_kernel(const int64_t* __restrict__ recs, int64_t m, int C,
+                                                                 uint32_t float_mask,
+                                                                 const int64_t* __restrict__ offsets, int64_t ng,
+                                                                 int64_t* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (t >= ng * C) return;
+  const int64_t g = t / C;
+  const int c = static_cast<int>(t - g * C);
+  const int64_t a = clamp64(offsets[g], 0, m), b = clamp64(offsets[g + 1], a, m);
+  const bool fl = (float_mask >> c) & 1u;
+  GRec r = grec_empty();
+  if (a < b) r = load_rec(recs + (a * C + c) * kGroupRecordFields);
+  for (int64_t i = a + 1; i < b; ++i) r = grec_merge(r, load_rec(recs + (i * C + c) * kGroupRecordFields), fl);
+  store_rec(out + t * kGroupRecordFields, r);
+}
+
+namespace {
+
+// the value of a float column's word, as f64
+__device__ __forceinline__ double word_value(uint64_t w, DType dt) {
+  return dt == DType::F32 ? static_cast<double>(__uint_as_float(decode_f32(w)))
+                          : bits_f64(decode_f64(w));
+}
+
+}  // namespace
+
+// thread g of block (.., o): output o of group g
+__global__ __launch_bounds__(kT) void group_results_kernel(const int64_t* __restrict__ recs, int64_t ng, int C,
+                                                           GroupResultSpec spec) {
+  const int o = blockIdx.y;
+  const int64_t g = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (g >= ng) return;
+  const int c = spec.col[o];
+  const DType dt = spec.dtype[o];
+  const GroupStat st = spec.stat[o];
+  const GRec r = load_rec(recs + (g * C + c) * kGroupRecordFields);
+  void* out = spec.out[o];
+  if (st == GroupStat::COUNT) {
+    static_cast<int64_t*>(out)[g] = static_cast<int64_t>(r.n);
+    return;
+  }
+  if (st == GroupStat::MIN || st == GroupStat::MAX) {
+    const bool has = r.n > 0.0;  // (a group without rows has no extreme: zero)
+    const uint64_t w = st == GroupStat::MIN ? r.lo : r.hi;
+    switch (dt) {
+      case DType::F32: static_cast<uint32_t*>(out)[g] = has ? decode_f32(w) : 0u; break;
+      case DType::F64: static_cast<uint64_t*>(out)[g] = has ? decode_f64(w) : 0ull; break;
+      case DType::I64: static_cast<int64_t*>(out)[g] = has ? decode_int(w) : 0; break;
+      case DType::I32: static_cast<int32_t*>(out)[g] = has ? static_cast<int32_t>(decode_int(w)) : 0; break;
+      case DType::I16: static_cast<int16_t*>(out)[g] = has ? static_cast<int16_t>(decode_int(w)) : 0; break;
+      case DType::I8: static_cast<int8_t*>(out)[g] = has ? static_cast<int8_t>(decode_int(w)) : 0; break;
+      default: static_cast<uint8_t*>(out)[g] = has ? static_cast<uint8_t>(w) : 0; break;  // U8
+    }
+    return;
+  }
+  const bool fl = float_dtype(dt);
+  if (st == GroupStat::SUM && !fl) {
+    static_cast<int64_t*>(out)[g] = static_cast<int64_t>(r.sum);
+    return;
+  }
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  double mean = r.n > 0.0 ? r.mean : nan, m2 = r.n > 0.0 ? r.m2 : nan, sum = fl ? bits_f64(r.sum) : 0.0;
+  if (r.n == 0.0) sum = 0.0;
+  if (fl && r.n > 0.0) {
+    // a NaN or an infinity propagates as in a plain sum / n, whatever the
+    // order the rows were met in: the extremes tell what is there
+    const double top = word_value(r.hi, dt), bottom = word_value(r.lo, dt);
+    if (top != top || (top == inf && bottom == -inf)) {
+      mean = m2 = sum = nan;
+    } else if (top == inf || bottom == -inf) {
+      mean = sum = top == inf ? inf : -inf;
+      m2 = nan;
+    }
+  }
+  double v;
+  switch (st) {
+    case GroupStat::SUM: v = sum; break;
+    case GroupStat::AVG: v = mean; break;
+    case GroupStat::VAR_SAMP: v = r.n >= 2.0 ? m2 / (r.n - 1.0) : nan; break;
+    case GroupStat::VAR_POP: v = r.n >= 1.0 ? m2 / r.n : nan; break;
+    case GroupStat::STDDEV_SAMP: v = r.n >= 2.0 ? sqrt(m2 / (r.n - 1.0)) : nan; break;
+    default: v = r.n >= 1.0 ? sqrt(m2 / r.n) : nan; break;  // STDDEV_POP
+  }
+  static_cast<double*>(out)[g] = v;
+}
+
+// ------------------------------------------------------------------ host API
+namespace {
+
+bool group_stat_dtype(DType d) {
+  return d == DType::F32 || d == DType::F64 || d == DType::I64 || d == DType::I32 || d == DType::I16 ||
+         d == DType::I8 || d == DType::U8;
+}
+
+int64_t max_chunks(int64_t nperm) { return std::max<int64_t>(1, (nperm + kGroupChunk - 1) / kGroupChunk); }
+
+size_t align8(size_t b) { return (b + 7) & ~size_t(7); }
+
+}  // namespace
+
+int group_chunk_rows() { return kGroupChunk; }
+
+// workspace: int64 cnt[nseg] | int64 coffs[nseg + 1] | join_scan's | records part[nseg + max_chunks][C]
+// (items = sum over segments of max(1, ceil(len / chunk)) <= nseg + nperm / chunk)
+size_t group_moments_workspace_bytes(int ncols, int64_t nperm, int64_t nseg) {
+  if (nseg <= 0 || ncols <= 0) return 0;
+  const size_t part = static_cast<size_t>(nseg + max_chunks(nperm)) * ncols * sizeof(GRec);
+  return align8(8 * nseg) + align8(8 * (nseg + 1)) + align8(join_scan_workspace_bytes(nseg)) + part;
+}
+
+void group_moments(const StatCols& cols, int64_t n, const int64_t* perm, int64_t nperm, const int64_t* offsets,
+                   int64_t nseg, int64_t* records, void* ws, size_t ws_size, hipStream_t s) {
+  TFA_CHECK(cols.n >= 1 && cols.n <= kMaxPackCols, "group_moments: 1..", kMaxPackCols, " columns, got ", cols.n);
+  TFA_CHECK(n >= 0 && nperm >= 0 && nperm <= n && nseg >= 0, "group_moments: bad row or segment count");
+  for (int c = 0; c < cols.n; ++c) {
+    TFA_CHECK(group_stat_dtype(cols.dtype[c]), "group_moments: column ", c, " has a dtype that is not supported");
+    TFA_CHECK(n == 0 || cols.ptr[c] != nullptr, "group_moments: column ", c, " has no data");
+    TFA_CHECK(reinterpret_cast<uintptr_t>(cols.ptr[c]) % static_cast<uintptr_t>(dtype_size(cols.dtype[c])) == 0,
+              "group_moments: column ", c, " is not aligned to its element size");
+  }
+  if (n == 0 || nseg == 0) return;
+  TFA_CHECK(nseg < (int64_t(1) << 31) && nseg + max_chunks(nperm) < (int64_t(1) << 31),
+            "group_moments: too many segments");
+  TFA_CHECK(perm != nullptr && offsets != nullptr && records != nullptr && ws != nullptr, "group_moments: null buffer");
+  TFA_CHECK(reinterpret_cast<uintptr_t>(records) % 8 == 0 && reinterpret_cast<uintptr_t>(ws) % 8 == 0,
+            "group_moments: unaligned buffer");
+  TFA_CHECK(ws_size >= group_moments_workspace_bytes(cols.n, nperm, nseg), "group_moments: workspace too small");
+  char* w = static_cast<char*>(ws);
+  int64_t* cnt = reinterpret_cast<int64_t*>(w);
+  w += align8(8 * nseg);
+  int64_t* coffs = reinterpret_cast<int64_t*>(w);
+  w += align8(8 * (nseg + 1));
+  void* scan_ws = w;
+  const size_t scan_bytes = align8(join_scan_workspace_bytes(nseg));
+  w += scan_bytes;
+  int64_t* part = reinterpret_cast<int64_t*>(w);
+  hipLaunchKernelGGL(group_chunk_count_kernel, dim3((unsigned)((nseg + kT - 1) / kT)), dim3(kT), 0, s, offsets, nseg,
+                     nperm, cnt);
+  TFA_LAUNCH_CHECK("group_chunk_count_kernel");
+  const int64_t items = join_scan(cnt, nseg, max_chunks(nperm), coffs, scan_ws, scan_bytes, s);  // (synchronises)
+  TFA_CHECK(items >= nseg && items <= nseg + max_chunks(nperm), "group_moments: ", items, " work items for ", nseg,
+            " segments of ", nperm, " rows");
+  const bool single = items == nseg;  // every segment is one chunk: item == segment
+  hipLaunchKernelGGL(group_moments_kernel, dim3((unsigned)((items + kWaves - 1) / kWaves), cols.n), dim3(kT), 0, s,
+                     cols, n, perm, nperm, offsets, (const int64_t*)coffs, nseg, items, single ? records : part);
+  TFA_LAUNCH_CHECK("group_moments_kernel");
+  if (single) return;
+  hipLaunchKernelGGL(group_fold_kernel, dim3((unsigned)((nseg * cols.n + kT - 1) / kT)), dim3(kT), 0, s, cols,
+                     (const int64_t*)part, (const int64_t*)coffs, nseg, items, records);
+  TFA_LAUNCH_CHECK("group_fold_kernel");
+}
+
+void merge_group_records(const int64_t* records, int64_t m, int ncols, uint32_t float_mask, const int64_t* offsets,
+                         int64_t ng, int64_t* out, hipStream_t s) {
+  TFA_CHECK(ncols >= 1 && ncols <= kMaxPackCols, "merge_group_records: 1..", kMaxPackCols, " columns, got ", ncols);
+  TFA_CHECK(m >= 0 && ng >= 0, "merge_group_records: negative count");
+  if (ng == 0) return;
+  TFA_CHECK(offsets != nullptr && out != nullptr && (m == 0 || records != nullptr), "merge_group_records: null buffer");
+  TFA_CHECK(ng * ncols < (int64_t(1) << 38), "merge_group_records: too many groups");
+  hipLaunchKernelGGL(merge_group_records_kernel, dim3((unsigned)((ng * ncols + kT - 1) / kT)), dim3(kT), 0, s, records,
+                     m, ncols, float_mask, offsets, ng, out);
+  TFA_LAUNCH_CHECK("merge_group_records_kernel");
+}
+
+void group_results(const int64_t* records, int64_t ng, int ncols, const GroupResultSpec& spec, hipStream_t s) {
+  TFA_CHECK(ncols >= 1 && ncols <= kMaxPackCols, "group_results: 1..", kMaxPackCols, " columns, got ", ncols);
+  TFA_CHECK(spec.n >= 1 && spec.n <= kMaxPackCols, "group_results: 1..", kMaxPackCols, " outputs, got ", spec.n);
+  TFA_CHECK(ng >= 0, "group_results: negative group count");
+  for (int o = 0; o < spec.n; ++o) {
+    TFA_CHECK(spec.col[o] >= 0 && spec.col[o] < ncols, "group_results: output ", o, " names column ", spec.col[o],
+              " of ", ncols);
+    TFA_CHECK(group_stat_dtype(spec.dtype[o]), "group_results: output ", o, " has a dtype that is not supported");
+    TFA_CHECK(static_cast<int>(spec.stat[o]) >= 0 && static_cast<int>(spec.stat[o]) <= static_cast<int>(GroupStat::STDDEV_POP),
+              "group_results: output ", o, " asks for an unknown statistic");
+    TFA_CHECK(ng == 0 || spec.out[o] != nullptr, "group_results: output ", o, " has no buffer");
+  }
+  if (ng == 0) return;
+  TFA_CHECK(records != nullptr, "group_results: null records");
+  TFA_CHECK((ng + kT - 1) / kT < (int64_t(1) << 31), "group_results: too many groups");
+  hipLaunchKernelGGL(group_results_kernel, dim3((unsigned)((ng + kT - 1) / kT), spec.n), dim3(kT), 0, s, records, ng,
+                     ncols, spec);
+  TFA_LAUNCH_CHECK("group_results_kernel");
+}
+
+}  // namespace k
+}  // namespace tfa

@@ -259,6 +259,43 @@ int stats_tile_rows();  // radix::kTile
 void select_hist(DType dtype, const void* col, int64_t n, const int64_t* prefixes, int P, int prefix_bits,
                  int64_t* hist, hipStream_t s);
 
+// ------------------------------------------------------------ grouped statistics (group_stats.hip)
+// GroupedData.agg / DataFrame.agg. A record is kGroupRecordFields int64 bit
+// patterns per (group, value column): n, mean, M2 (f64, every element
+// converted to f64 first), the sum (a wrapping int64 sum for the integer
+// dtypes, an f64 running sum for float32 / float64), the smallest and the
+// largest ascending sort word. An empty record is {0, 0, 0, 0, all ones, 0}.
+constexpr int kGroupRecordFields = 6;
+int group_chunk_rows();  // rows per work item of group_moments
+// records [nseg][cols.n][6] of the CSR segments (perm [nperm] row indices into
+// the columns' n rows, offsets [nseg + 1]: segment_csr's result). A work item
+// is at most group_chunk_rows() rows of one segment, taken by one wave
+// (Welford per lane, Chan's merge in lane order); a segment's items are folded
+// in chunk order. The chunk counts are scanned on the device and the stream
+// is synchronised once to read their total. A record depends on the
+// segment's rows in row order alone. n == 0 or nseg == 0 launches nothing.
+size_t group_moments_workspace_bytes(int ncols, int64_t nperm, int64_t nseg);
+void group_moments(const StatCols& cols, int64_t n, const int64_t* perm, int64_t nperm, const int64_t* offsets,
+                   int64_t nseg, int64_t* records, void* workspace, size_t workspace_size, hipStream_t s);
+// out [ng][ncols][6] = records [m][ncols][6] rows offsets[g] .. offsets[g + 1]
+// merged in order (Chan; integer sums add, float sums add in that order, words
+// take min / max), starting from the group's first record. Bit c of
+// float_mask: column c is float32 / float64
+void merge_group_records(const int64_t* records, int64_t m, int ncols, uint32_t float_mask, const int64_t* offsets,
+                         int64_t ng, int64_t* out, hipStream_t s);
+enum class GroupStat : int { COUNT = 0, SUM, AVG, MIN, MAX, VAR_SAMP, VAR_POP, STDDEV_SAMP, STDDEV_POP };
+struct GroupResultSpec {
+  int n = 0;
+  int col[kMaxPackCols];         // the record column an output reads
+  GroupStat stat[kMaxPackCols];
+  DType dtype[kMaxPackCols];     // that column's dtype
+  void* out[kMaxPackCols];       // [ng]: int64 (COUNT, SUM of integers), the column's type (MIN, MAX), else f64
+};
+// every output column of merged records [ng][ncols][6] in one launch: words
+// decoded to the column's type, describe's NaN / infinity rule (decided from
+// the extreme words), the sample statistics NaN below two rows
+void group_results(const int64_t* records, int64_t ng, int ncols, const GroupResultSpec& spec, hipStream_t s);
+
 // ------------------------------------------------------------ data movement
 // dst[idx] = src[idx] over `dims`, both operands addressed by element strides
 // (src strides may be 0 or negative; pointers already include the offsets).

@@ -29,6 +29,17 @@ __device__ __forceinline__ uint64_t encode_int(T v) {
   return static_cast<uint64_t>(static_cast<int64_t>(v)) ^ kSign64;
 }
 
+// the inverses: the bits (the value, for the integers) a word came from. Words
+// canonicalise, so -0.0 comes back as 0.0 and every NaN as the quiet NaN
+__device__ __forceinline__ uint32_t decode_f32(uint64_t w) {
+  const uint32_t e = static_cast<uint32_t>(w);
+  return (e & 0x80000000u) ? (e ^ 0x80000000u) : ~e;
+}
+
+__device__ __forceinline__ uint64_t decode_f64(uint64_t w) { return (w & kSign64) ? (w ^ kSign64) : ~w; }
+
+__device__ __forceinline__ int64_t decode_int(uint64_t w) { return static_cast<int64_t>(w ^ kSign64); }
+
 // the word of a typed value (BOOL / U8: the value)
 __device__ __forceinline__ uint64_t sort_word(float v) { return encode_f32(__float_as_uint(v)); }
 __device__ __forceinline__ uint64_t sort_word(double v) {

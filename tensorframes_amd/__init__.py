@@ -36,6 +36,7 @@ from .graph import dsl as tf  # noqa: F401
 from .operations import Operations, Ops, ShapeDescription, convert_block_to_row, explain_detailed, ops
 from .graph import dsl
 from . import scala_dsl  # noqa: F401  (the Scala DSL vocabulary)
+from . import functions  # noqa: F401  (named aggregates for groupBy(...).agg)
 from .parallel import dist
 from .utils.logging import initialize_logging, metrics
 from .utils.shape import Shape

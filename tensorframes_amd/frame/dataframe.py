@@ -591,6 +591,16 @@ class DataFrame:
 
     approx_quantile = approxQuantile
 
+    def agg(self, *exprs) -> "DataFrame":
+        """Named aggregates over the whole frame, `groupBy().agg(...)` without
+        keys: `agg(F.count("*"), F.avg("x"), F.max("x"))` with `tfs.functions`
+        as F, or `agg({"x": "sum"})`. One row, in one partition, identical on
+        every rank; names, types and values as in `GroupedData.agg`. A frame
+        without rows gives count 0, sum 0 and NaN for avg, stddev and variance;
+        a `min` or `max` of it raises ValueError. An action, and collective."""
+        from .group_agg import group_agg
+        return group_agg(GroupedData(self, []), list(exprs))
+
     @property
     def stat(self):
         """Spark's `df.stat` accessor (`df.stat.approxQuantile(...)`)."""
@@ -1095,6 +1105,46 @@ class GroupedData:
         with tf.Graph().as_default():
             ci = tf.placeholder(tf.int64, [None], name="count_input")
             return core.aggregate(tf.reduce_sum(ci, [0], name="count"), ones.groupBy(*keys))
+
+    def agg(self, *exprs) -> DataFrame:
+        """Named aggregates per key: `agg(F.avg("x"), F.stddev("x"), F.max("y"))`
+        with `tfs.functions` as F, or `agg({"x": "sum", "y": "max"})`. The
+        result holds the key columns, then one column per expression in call
+        order, named as Spark names them (`avg(x)`, `stddev_samp(x)`,
+        `count(1)`; `.alias()` overrides). count and integer sums are int64
+        (sums wrap), float sums, avg, stddev and variance float64, min / max
+        the column's own type. Keys are numeric scalar columns, grouped as
+        `groupBy(keys).count()` groups them; one output partition per rank,
+        keys in ascending order. Values follow `describe`: sample statistics
+        are NaN for a one-row group, a NaN in a group makes its sum, avg,
+        stddev and variance NaN, min / max order NaN last and return -0.0 as
+        0.0. Device-resident partitions are reduced by the grouped-moments
+        kernel (kernels/group_stats.hip); for a given partitioning the result
+        has the same bits for every number of ranks."""
+        from .group_agg import group_agg
+        return group_agg(self, list(exprs))
+
+    def sum(self, *cols) -> DataFrame:
+        """`agg(F.sum(c), ...)` of the named columns, or of every numeric scalar column that is not a key."""
+        from .group_agg import group_stat
+        return group_stat(self, "sum", cols)
+
+    def avg(self, *cols) -> DataFrame:
+        """`agg(F.avg(c), ...)` of the named columns, or of every numeric scalar column that is not a key."""
+        from .group_agg import group_stat
+        return group_stat(self, "avg", cols)
+
+    mean = avg
+
+    def min(self, *cols) -> DataFrame:
+        """`agg(F.min(c), ...)` of the named columns, or of every numeric scalar column that is not a key."""
+        from .group_agg import group_stat
+        return group_stat(self, "min", cols)
+
+    def max(self, *cols) -> DataFrame:
+        """`agg(F.max(c), ...)` of the named columns, or of every numeric scalar column that is not a key."""
+        from .group_agg import group_stat
+        return group_stat(self, "max", cols)
 
 
 def _sort_key(k):

@@ -1,0 +1,437 @@
+"""GroupedData.agg / DataFrame.agg: named aggregates over numeric keys.
+
+Per group and value column one record of six 8-byte fields travels as int64
+bit patterns: n, mean, M2 (f64; every element converted to f64 first), the sum
+(wrapping int64 for integer columns, an f64 running sum for float ones), and
+the smallest and largest ascending sort word.
+
+* stage 1: every partition is reduced on its own. Keys are factorised by
+  `ops/groupby.group_ids` (the grouping of `groupBy(keys).count()`); device
+  partitions go through `_C.segment_csr` + `_C.group_moments`
+  (kernels/group_stats.hip), host partitions through numpy (two-pass f64 per
+  group). One record per (group of the partition, column).
+* stage 2: the records of all partitions, tagged with their partition id,
+  are routed to the rank their key hashes to (`ops/groupby.route`: one
+  all-to-all, the partition id and the record fields riding as ordinary
+  columns), ordered by (keys..., partition id) with `group_ids`, and the
+  records of equal key are merged in ascending partition id with Chan's
+  formula (`_C.merge_group_records`, or `_merge_records` on the host).
+
+For a given partitioning every output bit is the same for every world size
+and from run to run: a record depends on its group's rows in row order
+alone, and the merge order is the partition order. No float atomics.
+"""
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ..functions import FUNCTIONS, AggregateExpression
+from ..parallel import dist
+from ..utils import dtypes as D
+from .block import Block
+from .column_info import ColumnInformation
+from .stats import _decode_sort_word, _ineligible, _scalar_column, _stat_columns
+from .types import BinaryType, StringType, StructType
+
+_FIELDS = 6  # kernels.h kGroupRecordFields
+_MAX_COLS = 16  # value columns per agg call, outputs per _C.group_results call (kernels.h kMaxPackCols)
+_KEY_DTYPES = (D.DT_INT32, D.DT_INT64, D.DT_FLOAT, D.DT_DOUBLE)
+_N, _MEAN, _M2, _SUM, _LO, _HI = range(_FIELDS)
+
+
+# ------------------------------------------------------------------ expressions
+class _Spec:
+    """One output column: statistic `fn` of value column `column` (None: rows)."""
+
+    def __init__(self, fn: str, column: Optional[str], name: str):
+        self.fn, self.column, self.name = fn, column, name
+
+
+def _tf_dtype(df, name: str) -> int:
+    return ColumnInformation(df.schema[name]).stf.tf_dtype
+
+
+def _specs(df, keys: Sequence[str], exprs: Sequence[Any], what: str) -> List[_Spec]:
+    if len(exprs) == 1 and isinstance(exprs[0], dict):
+        made = []
+        for col, fn in exprs[0].items():
+            if not isinstance(col, str) or not isinstance(fn, str):
+                raise TypeError(f"{what}: the dict form maps column names to function names, got {col!r}: {fn!r}")
+            if fn.lower() not in FUNCTIONS:
+                raise ValueError(f"{what}: '{fn}' is not an aggregate function; expected one of "
+                                 f"{', '.join(sorted(FUNCTIONS))}")
+            stat = FUNCTIONS[fn.lower()]
+            made.append(AggregateExpression(stat, None if (col == "*" and stat == "count") else col))
+        exprs = made
+    if not exprs:
+        raise ValueError(f"{what}: at least one aggregate expression is expected")
+    out: List[_Spec] = []
+    for e in exprs:
+        if not isinstance(e, AggregateExpression):
+            hint = " (Column.sum() and friends reduce the cell of one row; use tfs.functions.sum(name))" \
+                if type(e).__name__ == "Column" else ""
+            raise TypeError(f"{what}: aggregate expressions from tfs.functions are expected, got "
+                            f"{type(e).__name__}{hint}")
+        if e.column is not None:
+            if e.column not in df.schema:
+                raise ValueError(f"{what}: Column {e.column} not found in {df.columns}")
+            if e.fn != "count":  # (frames hold no nulls: count(x) counts rows, whatever x holds)
+                err = _ineligible(df, e.column, what)
+                if err is not None:
+                    raise err
+        out.append(_Spec(e.fn, e.column if e.fn != "count" else None, e.output_name))
+    seen = set(keys)
+    for s in out:
+        if s.name in seen:
+            raise ValueError(f"{what}: the output column '{s.name}' appears twice (or is a key); use .alias() to "
+                             f"rename one")
+        seen.add(s.name)
+    return out
+
+
+def _check_keys(df, keys: Sequence[str], what: str) -> None:
+    from .. import core
+    for k in keys:
+        f = df.schema[k]
+        if isinstance(f.dataType, (StringType, BinaryType)):
+            raise core.InvalidTypeException(
+                f"{what}: the key '{k}' is a {type(f.dataType).__name__[:-4].lower()} column; named aggregates take "
+                f"numeric scalar keys (int32, int64, float32, float64). String and binary keys are grouped by "
+                f"groupBy(...).aggregate(fetches)")
+        stf = ColumnInformation(f).stf
+        if stf is None or stf.tf_dtype not in _KEY_DTYPES or stf.shape.num_dims != 1:
+            raise core.InvalidTypeException(
+                f"{what}: the key '{k}' ({f.dataType}) is not a numeric scalar column of int32, int64, float32 or "
+                f"float64")
+
+
+def _out_dtype(df, s: _Spec) -> torch.dtype:
+    if s.fn == "count":
+        return torch.int64
+    vt = D.torch_dtype(_tf_dtype(df, s.column))
+    if s.fn == "sum":
+        return torch.float64 if vt.is_floating_point else torch.int64
+    return vt if s.fn in ("min", "max") else torch.float64
+
+
+# ------------------------------------------------------------------ host records
+def _f64(a: np.ndarray) -> np.ndarray:
+    return a.view(np.float64)
+
+
+def _host_group_records(vals: Sequence[torch.Tensor], ids: np.ndarray, ng: int) -> np.ndarray:
+    """int64 [ng, C, 6]: the records of one host partition (every group has rows).
+    Per group the two-pass form of stats._host_record."""
+    from .dataframe import _host_sort_words
+    out = np.zeros((ng, len(vals), _FIELDS), dtype=np.int64)
+    order = np.argsort(ids, kind="stable")
+    counts = np.bincount(ids, minlength=ng).astype(np.int64)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    nf = counts.astype(np.float64)
+    for c, v in enumerate(vals):
+        a = v.detach().contiguous().numpy()[order]
+        with np.errstate(all="ignore"):
+            x = a.astype(np.float64)
+            s = np.add.reduceat(x, starts)
+            mean = s / nf
+            dev = x - np.repeat(mean, counts)
+            # (two passes; the second also takes out what rounding left in the mean)
+            mean = mean + np.add.reduceat(dev, starts) / nf
+            dev = x - np.repeat(mean, counts)
+            m2 = np.add.reduceat(dev * dev, starts)
+        w = _host_sort_words(v, False)[order]
+        _f64(out[:, c, :3])[:, 0] = nf
+        _f64(out[:, c, :3])[:, 1] = mean
+        _f64(out[:, c, :3])[:, 2] = m2
+        out[:, c, _SUM] = s.view(np.int64) if a.dtype.kind == "f" else np.add.reduceat(a.astype(np.int64), starts)
+        out[:, c, _LO] = np.minimum.reduceat(w, starts).view(np.int64)
+        out[:, c, _HI] = np.maximum.reduceat(w, starts).view(np.int64)
+    return out
+
+
+def _chan(a: np.ndarray, b: np.ndarray, is_float: Sequence[bool]) -> np.ndarray:
+    """Chan's merge of records [s, C, 6], `a` the earlier rows (the arithmetic
+    of kernels/group_stats.hip grec_merge)."""
+    r = np.empty_like(a)
+    fa, fb, fr = _f64(a[..., :3]), _f64(b[..., :3]), _f64(r[..., :3])
+    an, bn = fa[..., 0], fb[..., 0]
+    with np.errstate(all="ignore"):
+        n = an + bn
+        delta = fb[..., 1] - fa[..., 1]
+        f = np.where(n > 0, bn / np.where(n > 0, n, 1.0), 0.0)
+        fr[..., 0] = n
+        fr[..., 1] = np.where(an == 0, fb[..., 1], np.where(bn == 0, fa[..., 1], fa[..., 1] + delta * f))
+        fr[..., 2] = np.where(an == 0, fb[..., 2],
+                              np.where(bn == 0, fa[..., 2], fa[..., 2] + fb[..., 2] + delta * delta * (an * f)))
+        fsum = np.where(an == 0, _f64(b[..., _SUM]),
+                        np.where(bn == 0, _f64(a[..., _SUM]), _f64(a[..., _SUM]) + _f64(b[..., _SUM])))
+        isum = a[..., _SUM] + b[..., _SUM]  # (int64: wraps)
+    r[..., _SUM] = np.where(np.asarray(is_float, dtype=bool)[None, :], fsum.view(np.int64), isum)
+    r[..., _LO] = np.minimum(a[..., _LO].view(np.uint64), b[..., _LO].view(np.uint64)).view(np.int64)
+    r[..., _HI] = np.maximum(a[..., _HI].view(np.uint64), b[..., _HI].view(np.uint64)).view(np.int64)
+    return r
+
+
+def _merge_records(recs: np.ndarray, offsets: np.ndarray, is_float: Sequence[bool]) -> np.ndarray:
+    """recs [m, C, 6] ordered by (key, partition), CSR offsets [ng + 1] (every
+    group has a record) -> [ng, C, 6]: each group's records merged in order,
+    starting from its first."""
+    recs = np.ascontiguousarray(recs)
+    counts = np.diff(offsets)
+    out = recs[offsets[:-1]].copy()
+    for j in range(1, int(counts.max()) if len(counts) else 0):
+        sel = np.nonzero(counts > j)[0]
+        out[sel] = _chan(out[sel], recs[offsets[sel] + j], is_float)
+    return out
+
+
+def _host_results(recs: np.ndarray, cols: Sequence[int], stats: Sequence[str], dtypes: Sequence[np.dtype]):
+    """Merged records [ng, C, 6] -> one numpy column per output (the host form
+    of `_C.group_results`)."""
+    outs = []
+    for ci, st, dt in zip(cols, stats, dtypes):
+        r = np.ascontiguousarray(recs[:, ci, :])
+        n = _f64(r[:, _N]).copy()
+        if st == "count":
+            outs.append(n.astype(np.int64))
+            continue
+        lo, hi = r[:, _LO].view(np.uint64), r[:, _HI].view(np.uint64)
+        if st in ("min", "max"):
+            v = np.asarray(_decode_sort_word(lo if st == "min" else hi, dt)).reshape(-1).copy()
+            v[n == 0] = 0
+            outs.append(v.astype(dt))
+            continue
+        fl = dt.kind == "f"
+        if st == "sum" and not fl:
+            outs.append(r[:, _SUM].copy())
+            continue
+        with np.errstate(all="ignore"):
+            mean = np.where(n > 0, _f64(r[:, _MEAN]), np.nan)
+            m2 = np.where(n > 0, _f64(r[:, _M2]), np.nan)
+            total = np.where(n > 0, _f64(r[:, _SUM]), 0.0) if fl else None
+            if fl:
+                # a NaN or an infinity propagates as in a plain sum / n, whatever the
+                # order the rows were met in: the extremes tell what is there
+                top = np.asarray(_decode_sort_word(hi, dt), dtype=np.float64).reshape(-1)
+                bottom = np.asarray(_decode_sort_word(lo, dt), dtype=np.float64).reshape(-1)
+                has = n > 0
+                bad = has & (np.isnan(top) | ((top == np.inf) & (bottom == -np.inf)))
+                one = has & ~bad & ((top == np.inf) | (bottom == -np.inf))
+                signed = np.where(top == np.inf, np.inf, -np.inf)
+                mean = np.where(bad, np.nan, np.where(one, signed, mean))
+                total = np.where(bad, np.nan, np.where(one, signed, total))
+                m2 = np.where(bad | one, np.nan, m2)
+            if st == "sum":
+                v = total
+            elif st == "avg":
+                v = mean
+            elif st in ("var_samp", "stddev_samp"):
+                v = np.where(n >= 2, m2 / np.where(n >= 2, n - 1, 1.0), np.nan)
+            else:
+                v = np.where(n >= 1, m2 / np.where(n >= 1, n, 1.0), np.nan)
+            if st.startswith("stddev"):
+                v = np.sqrt(v)
+        outs.append(np.asarray(v, dtype=np.float64))
+    return outs
+
+
+# ------------------------------------------------------------------ stage 1
+def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_device: bool, what: str):
+    """(distinct key columns of the partition, records [ng, C, 6] int64) of
+    one non-empty partition, on the device or on the host."""
+    from .. import core, engine
+    from .._native import _C
+    from ..ops import groupby as G
+    from ..utils.logging import metrics
+    dev = engine.compute_device() if on_device else torch.device("cpu")
+    vals = [_scalar_column(b, v, what).to(dev) for v in vcols]
+    if not vals:  # only rows are counted: a column of zeros carries n
+        vals = [engine.device_full(b.nrows, 0, torch.uint8, dev)]
+    if keys:
+        K = [b.columns[k] for k in keys]
+        if not G.device_keys(K):
+            raise core.InvalidDimensionException(
+                f"{what}: a key column does not hold one numeric scalar per row in this partition")
+        ids, uniq, ng = G.group_ids([k.to(dev).contiguous() for k in K])
+    else:
+        ids, uniq, ng = engine.device_full(b.nrows, 0, torch.int64, dev), [], 1
+    if on_device:
+        perm, offsets = _C.segment_csr(ids, ng)
+        recs = _C.group_moments([v.contiguous() for v in vals], perm, offsets)
+        metrics.add("group_agg_device_partitions")
+    else:
+        recs = torch.from_numpy(_host_group_records(vals, ids.numpy(), ng))
+        metrics.add("group_agg_host_partitions")
+    metrics.add("group_agg_rows", b.nrows * len(vals))
+    return uniq, recs
+
+
+def _needed(keys, vcols):
+    return list(keys) + [v for v in vcols if v not in keys]
+
+
+def _block_on_device(b: Block, names: Sequence[str]) -> bool:
+    return all(isinstance(b.columns[n], torch.Tensor) and b.columns[n].is_cuda for n in names)
+
+
+# ------------------------------------------------------------------ keyed
+def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
+    """`GroupedData.agg`: see there."""
+    from .. import engine
+    from .._native import _C
+    from ..ops import groupby as G
+    from .dataframe import DataFrame, _Derived, tensor_field
+    df, keys = grouped.df, list(grouped.keys)
+    specs = _specs(df, keys, exprs, what)
+    if not keys:
+        return frame_agg(df, specs, what)
+    _check_keys(df, keys, what)
+    vcols: List[str] = []
+    for s in specs:
+        if s.column is not None and s.column not in vcols:
+            vcols.append(s.column)
+    if len(vcols) > _MAX_COLS:
+        raise ValueError(f"{what}: at most {_MAX_COLS} distinct value columns per call, got {len(vcols)}; split the "
+                         f"call and join the results on the keys")
+    C = max(len(vcols), 1)
+    vdt = [D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]
+    is_float = [t.is_floating_point for t in vdt]
+    kdt = [D.torch_dtype(_tf_dtype(df, k)) for k in keys]
+    out_dt = [_out_dtype(df, s) for s in specs]
+    scol = [vcols.index(s.column) if s.column is not None else 0 for s in specs]
+    needed = _needed(keys, vcols)
+    keep_on_device = any(b.columns[n].is_cuda for b in (df._cached or {}).values() if b.nrows for n in needed
+                         if isinstance(b.columns[n], torch.Tensor))
+    world = max(1, dist.world_size())
+
+    def empty():
+        cols: Dict[str, Any] = {k: torch.empty(0, dtype=t) for k, t in zip(keys, kdt)}
+        cols.update({s.name: torch.empty(0, dtype=t) for s, t in zip(specs, out_dt)})
+        return {p: Block(0, dict(cols)) for p in dist.local_partitions(world)}
+
+    def compute(blocks):
+        parts = [(pid, b) for pid, b in sorted(blocks.items()) if b.nrows]
+        # decided together, so every rank takes the same (collective) path:
+        # the device path when no rank holds a needed column on the host
+        flags = torch.tensor([int(any(not _block_on_device(b, needed) for _, b in parts)), int(bool(parts))],
+                             dtype=torch.int64)
+        dist.all_reduce_host_(flags, "Max")
+        if not int(flags[1]):
+            return empty()
+        on_device = engine.gpu_available() and not int(flags[0])
+        dev = engine.compute_device() if on_device else torch.device("cpu")
+        got = [(pid,) + _partition_records(b, keys, vcols, on_device, what) for pid, b in parts]
+        if got:
+            K = [engine.cat_rows([u[j] for _, u, _ in got]) for j in range(len(keys))]
+            R = engine.cat_rows([r.reshape(r.shape[0], C * _FIELDS) for _, _, r in got])
+            pids = engine.cat_rows([engine.device_full(r.shape[0], pid, torch.int64, dev) for pid, _, r in got])
+        else:
+            K = [engine.device_empty(0, t, dev) for t in kdt]
+            R = engine.device_empty((0, C * _FIELDS), torch.int64, dev)
+            pids = engine.device_empty(0, torch.int64, dev)
+        if not dist.is_distributed() and len(got) == 1:
+            ukeys, merged = K, R.reshape(-1, C, _FIELDS)  # one partition: its records are the result
+        else:
+            if dist.is_distributed():
+                recv = G.route(K, [pids, R])
+                K, pids, R = recv[:len(keys)], recv[len(keys)], recv[len(keys) + 1]
+            m = int(K[0].shape[0])
+            if m == 0:
+                return empty()
+            # (keys..., partition id) in lexicographic order: the records of one
+            # key are consecutive and in partition order
+            ids, uniq, m2 = G.group_ids([k.contiguous() for k in K] + [pids])
+            if m2 != m:
+                raise RuntimeError(f"{what}: {m} records but {m2} distinct (key, partition) pairs")
+            ordered = engine.device_empty((m, C * _FIELDS), torch.int64, dev)
+            if on_device:
+                _C.scatter_rows(ordered, ids, R.contiguous())
+            else:
+                ordered[ids] = R
+            ids2, ukeys, ng = G.group_ids([u.contiguous() for u in uniq[:-1]])
+            if on_device:
+                _, offsets = _C.segment_csr(ids2, ng)
+                merged = _C.merge_group_records(ordered.reshape(m, C, _FIELDS), offsets, is_float)
+            else:
+                offsets = np.concatenate([[0], np.cumsum(np.bincount(ids2.numpy(), minlength=ng))]).astype(np.int64)
+                merged = torch.from_numpy(_merge_records(ordered.numpy().reshape(m, C, _FIELDS), offsets, is_float))
+        ng = int(merged.shape[0])
+        outs: List[torch.Tensor] = []
+        for a in range(0, len(specs), _MAX_COLS):
+            sl = slice(a, a + _MAX_COLS)
+            if on_device:
+                outs.extend(_C.group_results(merged.contiguous(), scol[sl], [s.fn for s in specs[sl]],
+                                             [vdt[c] for c in scol[sl]]))
+            else:
+                np_dt = [torch.empty(0, dtype=vdt[c]).numpy().dtype for c in scol[sl]]
+                outs.extend(torch.from_numpy(np.ascontiguousarray(o)) for o in
+                            _host_results(merged.numpy(), scol[sl], [s.fn for s in specs[sl]], np_dt))
+        keep = on_device and keep_on_device
+        cols: Dict[str, Any] = {k: (u if keep else u.cpu()) for k, u in zip(keys, ukeys)}
+        cols.update({s.name: (o if keep else o.cpu()) for s, o in zip(specs, outs)})
+        return {dist.rank(): Block(ng, cols)}
+
+    def compute_agreed(blocks):
+        return dist.agreed(what, lambda: compute(blocks))
+
+    fields = [df.schema[k] for k in keys] + [tensor_field(s.name, t, []) for s, t in zip(specs, out_dt)]
+    return DataFrame(StructType(fields), _Derived(df, compute_agreed, streamable=False), world)
+
+
+# ------------------------------------------------------------------ no keys
+def frame_agg(df, specs, what: str = "agg"):
+    """`DataFrame.agg`: one row, in one partition, identical on every rank
+    (an action, and collective, like `describe`)."""
+    from .dataframe import from_columns
+    if not isinstance(specs, list) or not all(isinstance(s, _Spec) for s in specs):
+        specs = _specs(df, [], list(specs), what)
+    vcols: List[str] = []
+    for s in specs:
+        if s.column is not None and s.column not in vcols:
+            vcols.append(s.column)
+    if len(vcols) > _MAX_COLS:
+        raise ValueError(f"{what}: at most {_MAX_COLS} distinct value columns per call, got {len(vcols)}")
+    C = max(len(vcols), 1)
+    vdt = [D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]
+    is_float = [t.is_floating_point for t in vdt]
+    scol = [vcols.index(s.column) if s.column is not None else 0 for s in specs]
+
+    def run():
+        from .. import engine
+        blocks = df._blocks()
+        table = torch.zeros((df.num_partitions, C, _FIELDS), dtype=torch.int64)
+        for pid in sorted(blocks):
+            b = blocks[pid]
+            if b.nrows:
+                on_device = engine.gpu_available() and _block_on_device(b, vcols) and bool(vcols)
+                table[pid] = _partition_records(b, [], vcols, on_device, what)[1].cpu()[0]
+        dist.all_reduce_host_(table, "Sum")  # (every rank fills the rows of its own partitions; the others are zero)
+        return table.numpy()
+    table = dist.agreed(what, run)
+    recs = table[_f64(np.ascontiguousarray(table[:, 0, _N])) > 0]  # the partitions with rows, in partition order
+    if len(recs):
+        merged = _merge_records(recs, np.array([0, len(recs)], dtype=np.int64), is_float)
+    else:
+        for s in specs:
+            if s.fn in ("min", "max"):
+                raise ValueError(f"{what}: {s.fn}({s.column}) of a frame without rows does not exist")
+        merged = np.zeros((1, C, _FIELDS), dtype=np.int64)
+    np_dt = [torch.empty(0, dtype=vdt[c]).numpy().dtype for c in scol]
+    outs = _host_results(merged, scol, [s.fn for s in specs], np_dt)
+    return from_columns({s.name: np.ascontiguousarray(o) for s, o in zip(specs, outs)}, num_partitions=1)
+
+
+# ------------------------------------------------------------------ shortcuts
+def group_stat(grouped, fn: str, cols: Sequence[Any]):
+    """`GroupedData.sum / avg / mean / min / max`: the named columns, or every
+    numeric scalar column that is not a key."""
+    df = grouped.df
+    names = _stat_columns(df, cols, fn)
+    if not [c for cs in cols for c in (cs if isinstance(cs, (list, tuple)) else [cs])]:
+        names = [n for n in names if n not in grouped.keys]
+    if not names:
+        raise ValueError(f"{fn}: the frame has no numeric scalar column besides the keys")
+    return group_agg(grouped, [AggregateExpression(FUNCTIONS[fn], n) for n in names], fn)

@@ -1,0 +1,125 @@
+"""Named aggregate functions for `GroupedData.agg` / `DataFrame.agg`.
+
+    from tensorframes_amd import functions as F
+    scored.groupBy("id").agg(F.avg("score"), F.stddev("score"), F.max("score"))
+
+Each function takes a column name or a plain column reference (`tfs.col("x")`,
+`df["x"]`) and returns an `AggregateExpression`; `.alias(name)` renames its
+output column. These reduce a column over the rows of a group. They are not
+`Column.sum()` and friends, which reduce the cell of one row.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+from .frame.column import Column
+
+__all__ = ["AggregateExpression", "count", "sum", "avg", "mean", "min", "max", "stddev", "stddev_samp", "stddev_pop",
+           "variance", "var_samp", "var_pop"]
+
+# the canonical statistic behind every accepted name (the dict form of agg uses the same table)
+FUNCTIONS = {
+    "count": "count", "sum": "sum", "avg": "avg", "mean": "avg", "min": "min", "max": "max",
+    "stddev": "stddev_samp", "stddev_samp": "stddev_samp", "stddev_pop": "stddev_pop",
+    "variance": "var_samp", "var_samp": "var_samp", "var_pop": "var_pop",
+}
+
+
+class AggregateExpression:
+    """One aggregate of one column: `fn` is the canonical statistic, `column`
+    the value column's name (None for `count("*")` / `count(1)`)."""
+
+    __slots__ = ("fn", "column", "_alias")
+
+    def __init__(self, fn: str, column: Optional[str], alias: Optional[str] = None):
+        self.fn = fn
+        self.column = column
+        self._alias = alias
+
+    def alias(self, name: str) -> "AggregateExpression":
+        if not isinstance(name, str) or not name:
+            raise TypeError(f"alias: a non-empty column name is expected, got {name!r}")
+        return AggregateExpression(self.fn, self.column, name)
+
+    name = alias
+
+    @property
+    def output_name(self) -> str:
+        if self._alias is not None:
+            return self._alias
+        return f"{self.fn}({self.column if self.column is not None else 1})"
+
+    def __repr__(self):
+        return f"AggregateExpression<{self.output_name}>"
+
+
+def _make(fn: str, col) -> AggregateExpression:
+    if isinstance(col, Column):
+        if not col.is_reference:
+            raise TypeError(f"{fn}: '{col.output_name}' is a computed Column; aggregates take a column name or a "
+                            f"plain column reference. Add it to the frame first: df.withColumn(name, expr), then "
+                            f"{fn}(name)")
+        if col.sort_order is not None:
+            raise TypeError(f"{fn}: '{col.output_name}.{col.sort_order}()' is a sort order, not a column")
+        return AggregateExpression(FUNCTIONS[fn], col._expr[1])
+    if not isinstance(col, str):
+        raise TypeError(f"{fn}: a column name or a column reference is expected, got {type(col).__name__}")
+    return AggregateExpression(FUNCTIONS[fn], col)
+
+
+def count(col) -> AggregateExpression:
+    """Rows per group. `count("*")` and `count(1)` count rows; frames hold no
+    nulls, so `count(x)` is the same number."""
+    if (isinstance(col, str) and col == "*") or (isinstance(col, int) and not isinstance(col, bool) and col == 1):
+        return AggregateExpression("count", None)
+    return _make("count", col)
+
+
+def sum(col) -> AggregateExpression:  # noqa: A001
+    """int64 (wrapping) for integer columns, float64 for float32 / float64."""
+    return _make("sum", col)
+
+
+def avg(col) -> AggregateExpression:
+    return _make("avg", col)
+
+
+def mean(col) -> AggregateExpression:
+    """The same as `avg`."""
+    return _make("mean", col)
+
+
+def min(col) -> AggregateExpression:  # noqa: A001
+    """The smallest value in `orderBy`'s order, in the column's own type."""
+    return _make("min", col)
+
+
+def max(col) -> AggregateExpression:  # noqa: A001
+    """The largest value in `orderBy`'s order (NaN after +inf), in the column's own type."""
+    return _make("max", col)
+
+
+def stddev(col) -> AggregateExpression:
+    """The sample standard deviation (NaN for a group of one row)."""
+    return _make("stddev", col)
+
+
+def stddev_samp(col) -> AggregateExpression:
+    return _make("stddev_samp", col)
+
+
+def stddev_pop(col) -> AggregateExpression:
+    return _make("stddev_pop", col)
+
+
+def variance(col) -> AggregateExpression:
+    """The sample variance (NaN for a group of one row)."""
+    return _make("variance", col)
+
+
+def var_samp(col) -> AggregateExpression:
+    return _make("var_samp", col)
+
+
+def var_pop(col) -> AggregateExpression:
+    return _make("var_pop", col)
