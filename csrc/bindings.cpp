@@ -1164,6 +1164,168 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "values have dtype dtypes[o]. count and integer sums are int64, min / max the column's dtype (words decoded: "
      "-0.0 comes back as 0.0), the others float64; a NaN or opposite infinities in a float group give NaN, the "
      "sample statistics NaN below two rows");
+  // Window / .over() on device-resident partitions (kernels/window_scan.hip)
+  m.def("window_tile_rows", [] { return k::window_tile_rows(); }, "rows per tile of window_scan");
+  // int64 device bit patterns [rows, n], contiguous
+  auto window_table = [](const char* what, const char* which, const at::Tensor& t) {
+    if (!t.is_cuda()) throw py::value_error(str_cat(what, ": ", which, " must be a device tensor"));
+    if (t.scalar_type() != at::kLong) throw py::type_error(str_cat(what, ": ", which, " must be int64 bit patterns"));
+    if (t.dim() != 2) throw py::value_error(str_cat(what, ": ", which, " must be 2-D [*, n]"));
+    if (!t.is_contiguous()) throw py::value_error(str_cat(what, ": ", which, " is not contiguous"));
+  };
+  m.def("window_scan", [stat_column, window_table](const at::Tensor& words, int64_t P, bool reverse,
+                                                   const std::vector<std::string>& kinds,
+                                                   const std::vector<at::Tensor>& cols) {
+    static const char* const names[] = {"group_head", "peer_head", "peer_count", "sum_i64", "sum_f64", "min_word",
+                                        "max_word"};
+    window_table("window_scan", "the words", words);
+    const int64_t W = words.size(0), n = words.size(1);
+    if (W > k::kMaxSortKeys)
+      throw py::value_error(str_cat("window_scan: at most ", k::kMaxSortKeys, " words per row, got ", W));
+    if (P < 0 || P > W) throw py::value_error(str_cat("window_scan: 0 <= P <= ", W, " expected, got ", P));
+    if (kinds.empty() || kinds.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("window_scan: 1..", k::kMaxPackCols, " channels per call, got ", kinds.size()));
+    k::WindowChans ch;
+    ch.n = static_cast<int>(kinds.size());
+    size_t used = 0;
+    for (size_t c = 0; c < kinds.size(); ++c) {
+      int kd = -1;
+      for (int i = 0; i < 7; ++i)
+        if (kinds[c] == names[i]) kd = i;
+      if (kd < 0) throw py::value_error(str_cat("window_scan: '", kinds[c], "' is not a channel kind"));
+      ch.kind[c] = kd;
+      ch.dtype[c] = DType::U8;
+      ch.ptr[c] = nullptr;
+      if (kd < static_cast<int>(k::WindowChan::SUM_I64)) continue;
+      if (used >= cols.size())
+        throw py::value_error(str_cat("window_scan: channel ", c, " (", kinds[c], ") has no value column"));
+      const at::Tensor& t = cols[used++];
+      stat_column("window_scan", t, str_cat("the column of channel ", c));
+      if (t.device() != words.device())
+        throw py::value_error(str_cat("window_scan: the column of channel ", c, " is not on the words' device"));
+      if (t.size(0) != n)
+        throw py::value_error(str_cat("window_scan: the column of channel ", c, " has ", t.size(0),
+                                      " rows, the words ", n));
+      ch.dtype[c] = from_scalar_type(t.scalar_type());
+      ch.ptr[c] = t.data_ptr();
+    }
+    if (used != cols.size())
+      throw py::value_error(str_cat("window_scan: ", cols.size(), " value columns for ", used, " value channels"));
+    const int64_t C = ch.n;
+    if (n == 0) return at::empty({C, 0}, words.options());  // nothing is launched
+    c10::hip::HIPGuard guard(words.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(words.device().index()).stream();
+    at::Tensor out = pool_empty({C, n}, words.options());
+    const size_t wsb = k::window_scan_workspace_bytes(ch.n, n);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, words.options());
+    k::window_scan(W ? words.data_ptr<int64_t>() : nullptr, static_cast<int>(W), static_cast<int>(P), n, reverse, ch,
+                   out.data_ptr<int64_t>(), ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    return out;
+  }, py::arg("words"), py::arg("P"), py::arg("reverse"), py::arg("kinds"), py::arg("cols"),
+     "the words [W, n] of one sorted partition (int64 device bit patterns; the first P define groups, all W peers) "
+     "-> int64 [C, n]: one segmented inclusive scan per channel kind (group_head, peer_head: the head's row index; "
+     "peer_count; sum_i64, sum_f64, min_word, max_word of the next value column in cols). reverse scans the "
+     "mirrored rows: the index channels give the last row of the group / peer run. Three launches, no block waits "
+     "for another; the same bits on every run. n == 0 launches nothing");
+  m.def("window_finish", [window_table](const at::Tensor& fwd, const at::Tensor& rev,
+                                        const std::vector<std::string>& kinds, const std::vector<int64_t>& carry,
+                                        const std::vector<int64_t>& total, bool has_carry, bool has_total,
+                                        int64_t carry_rows, int64_t total_rows, const std::vector<std::string>& fns,
+                                        const std::vector<std::string>& frames, const std::vector<int64_t>& chans,
+                                        const std::vector<at::ScalarType>& dtypes) {
+    static const char* const kind_names[] = {"group_head", "peer_head", "peer_count", "sum_i64", "sum_f64",
+                                             "min_word", "max_word"};
+    static const char* const fn_names[] = {"row_number", "rank", "dense_rank", "count", "sum", "avg", "min", "max"};
+    static const char* const frame_names[] = {"rows", "range", "whole"};
+    window_table("window_finish", "the forward scan", fwd);
+    window_table("window_finish", "the reverse scan", rev);
+    const int64_t C = fwd.size(0), n = fwd.size(1);
+    if (rev.device() != fwd.device()) throw py::value_error("window_finish: the two scans are on different devices");
+    if (rev.size(0) != 2 || rev.size(1) != n)
+      throw py::value_error(str_cat("window_finish: a reverse scan [2, ", n, "] expected, got [", rev.size(0), ", ",
+                                    rev.size(1), "]"));
+    if (C < 2 || C > k::kMaxPackCols || static_cast<int64_t>(kinds.size()) != C ||
+        static_cast<int64_t>(carry.size()) != C || static_cast<int64_t>(total.size()) != C)
+      throw py::value_error(str_cat("window_finish: a forward scan of 2..", k::kMaxPackCols, " channels with one "
+                                    "kind, carry and total each expected, got ", C, " channels, ", kinds.size(),
+                                    " kinds, ", carry.size(), " carries, ", total.size(), " totals"));
+    if (fns.empty() || fns.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("window_finish: 1..", k::kMaxPackCols, " outputs per call, got ", fns.size()));
+    if (frames.size() != fns.size() || chans.size() != fns.size() || dtypes.size() != fns.size())
+      throw py::value_error("window_finish: one frame, channel and column dtype per output expected");
+    if (carry_rows < 0 || total_rows < 0) throw py::value_error("window_finish: negative row count");
+    k::WindowFinishSpec sp;
+    sp.n_chan = static_cast<int>(C);
+    std::vector<int> kd(C, -1);
+    for (int64_t c = 0; c < C; ++c) {
+      for (int i = 0; i < 7; ++i)
+        if (kinds[c] == kind_names[i]) kd[c] = i;
+      if (kd[c] < 0) throw py::value_error(str_cat("window_finish: '", kinds[c], "' is not a channel kind"));
+      sp.op[c] = k::window_chan_op(kd[c]);
+      sp.carry[c] = static_cast<uint64_t>(carry[c]);
+      sp.total[c] = static_cast<uint64_t>(total[c]);
+    }
+    if (kd[0] != 0 || kd[1] != 1)
+      throw py::value_error("window_finish: channels 0 and 1 of the forward scan must be group_head and peer_head");
+    sp.has_carry = has_carry ? 1 : 0;
+    sp.has_total = has_total ? 1 : 0;
+    sp.carry_rows = carry_rows;
+    sp.total_rows = total_rows;
+    sp.n_out = static_cast<int>(fns.size());
+    c10::hip::HIPGuard guard(fwd.device().index());
+    std::vector<at::Tensor> outs;
+    for (size_t o = 0; o < fns.size(); ++o) {
+      int fn = -1, fr = -1;
+      for (int i = 0; i < 8; ++i)
+        if (fns[o] == fn_names[i]) fn = i;
+      for (int i = 0; i < 3; ++i)
+        if (frames[o] == frame_names[i]) fr = i;
+      if (fn < 0) throw py::value_error(str_cat("window_finish: '", fns[o], "' is not a window function"));
+      if (fr < 0) throw py::value_error(str_cat("window_finish: '", frames[o], "' is not a frame"));
+      if (chans[o] < 0 || chans[o] >= C)
+        throw py::value_error(str_cat("window_finish: output ", o, " names channel ", chans[o], " of ", C));
+      const at::ScalarType ct = dtypes[o];
+      if (ct != at::kFloat && ct != at::kDouble && ct != at::kLong && ct != at::kInt && ct != at::kShort &&
+          ct != at::kChar && ct != at::kByte)
+        throw py::type_error(str_cat("window_finish: output ", o, " reads a ", c10::toString(ct), " column, which "
+                                     "is not supported (uint8, int8, int16, int32, int64, float32 or float64)"));
+      const auto wf = static_cast<k::WindowFn>(fn);
+      const int ck = kd[chans[o]];
+      at::ScalarType ot = at::kInt;
+      bool fits = true;
+      switch (wf) {
+        case k::WindowFn::ROW_NUMBER:
+        case k::WindowFn::RANK: break;
+        case k::WindowFn::DENSE_RANK: fits = ck == 2; break;
+        case k::WindowFn::COUNT: ot = at::kLong; break;
+        case k::WindowFn::SUM: fits = ck == 3 || ck == 4; ot = ck == 3 ? at::kLong : at::kDouble; break;
+        case k::WindowFn::AVG: fits = ck == 4; ot = at::kDouble; break;
+        case k::WindowFn::MIN: fits = ck == 5; ot = ct; break;
+        default: fits = ck == 6; ot = ct; break;  // MAX
+      }
+      if (!fits)
+        throw py::value_error(str_cat("window_finish: output ", o, " (", fns[o], ") cannot read a ",
+                                      kinds[chans[o]], " channel"));
+      outs.push_back(pool_empty({n}, fwd.options().dtype(ot)));
+      sp.fn[o] = wf;
+      sp.frame[o] = static_cast<k::WindowFrame>(fr);
+      sp.chan[o] = static_cast<int>(chans[o]);
+      sp.dtype[o] = from_scalar_type(ct);
+      sp.out[o] = outs.back().data_ptr();
+    }
+    if (n == 0) return outs;  // nothing is launched
+    k::window_finish(fwd.data_ptr<int64_t>(), rev.data_ptr<int64_t>(), n, sp,
+                     c10::hip::getCurrentHIPStream(fwd.device().index()).stream());
+    return outs;
+  }, py::arg("fwd"), py::arg("rev"), py::arg("kinds"), py::arg("carry"), py::arg("total"), py::arg("has_carry"),
+     py::arg("has_total"), py::arg("carry_rows"), py::arg("total_rows"), py::arg("fns"), py::arg("frames"),
+     py::arg("chans"), py::arg("dtypes"),
+     "a forward window_scan [C, n] (channels 0, 1: group_head, peer_head; kinds names all C) and a reverse scan "
+     "[2, n] of those two -> one device column [n] per output (up to 16, one launch): fns[o] (row_number, rank, "
+     "dense_rank: int32; count: int64; sum: int64 or float64 as its channel; avg: float64; min, max: dtypes[o]) over "
+     "frames[o] (rows, range, whole), read from channel chans[o]. carry[c] / carry_rows: the fold of the first "
+     "group's pieces in earlier partitions, applied on the left when has_carry; total[c] / total_rows: the whole-"
+     "group values of the last group when it runs on into a later partition (has_total)");
   // native JPEG decode into one ragged (pinned) buffer (runtime/jpeg_decode.cpp)
   struct PyJpegBatch {
     std::vector<py::buffer_info> views;  // keep the cells' buffers exported while decoding

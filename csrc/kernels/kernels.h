@@ -296,6 +296,61 @@ struct GroupResultSpec {
 // the extreme words), the sample statistics NaN below two rows
 void group_results(const int64_t* records, int64_t ng, int ncols, const GroupResultSpec& spec, hipStream_t s);
 
+// ------------------------------------------------------------ window functions (window_scan.hip)
+// Window / .over(). The n rows of one partition are sorted by (partition
+// keys, order keys) and come as sort_encode's words [W][n]. A row is a group
+// head when one of its first P words differs from the previous row's, a peer
+// head when one of the W words does; row 0 is both (P == 0: one group). A
+// channel is a segmented inclusive scan over the rows of a group, 8 bytes per
+// row:
+//   GROUP_HEAD / PEER_HEAD  the index of the row's group / peer head,
+//   PEER_COUNT              peer heads of the group up to the row (dense_rank),
+//   SUM_I64 / SUM_F64       the wrapping int64 / the f64 sum of a value column
+//                           (every element converted first),
+//   MIN_WORD / MAX_WORD     the smallest / largest ascending word of a column.
+// In reverse the scan runs over the mirrored rows: a head is a row that
+// differs from the next one, the two index channels give the last row of the
+// row's group / peer run, the others scan from the group's end.
+enum class WindowChan : int { GROUP_HEAD = 0, PEER_HEAD, PEER_COUNT, SUM_I64, SUM_F64, MIN_WORD, MAX_WORD };
+struct WindowChans {
+  int n = 0;
+  int kind[kMaxPackCols];          // WindowChan
+  DType dtype[kMaxPackCols];       // of the value column (SUM_I64 on)
+  const void* ptr[kMaxPackCols];   // [n], contiguous, aligned to the element (SUM_I64 on)
+};
+int window_tile_rows();  // rows per tile of window_scan
+// the operator a channel kind folds with: 0 wrapping int64 add, 1 f64 add, 2 / 3 unsigned min / max
+int window_chan_op(int kind);
+size_t window_scan_workspace_bytes(int nchan, int64_t n);
+// out [ch.n][n] (int64 bit patterns). Reduce-then-scan in three launches (tile
+// aggregates, one block over them, every tile again), no block waits for
+// another; the order of the additions depends on n and window_tile_rows()
+// alone. n == 0 launches nothing.
+void window_scan(const int64_t* words, int W, int P, int64_t n, bool reverse, const WindowChans& ch, int64_t* out,
+                 void* workspace, size_t workspace_size, hipStream_t s);
+enum class WindowFn : int { ROW_NUMBER = 0, RANK, DENSE_RANK, COUNT, SUM, AVG, MIN, MAX };
+enum class WindowFrame : int { ROWS = 0, RANGE, WHOLE };  // ..currentRow by rows, by peers; the whole group
+struct WindowFinishSpec {
+  int n_out = 0;
+  WindowFn fn[kMaxPackCols];
+  WindowFrame frame[kMaxPackCols];
+  int chan[kMaxPackCols];        // the forward channel an output reads (DENSE_RANK, SUM, AVG, MIN, MAX)
+  DType dtype[kMaxPackCols];     // the value column's dtype (MIN, MAX decode to it)
+  void* out[kMaxPackCols];       // [n]: int32 (ranks), int64 (COUNT, SUM of SUM_I64), f64 (SUM of SUM_F64, AVG), the column's type
+  int n_chan = 0;
+  int op[kMaxPackCols];          // window_chan_op of every forward channel
+  uint64_t carry[kMaxPackCols];  // the fold of the first group's pieces in earlier partitions
+  uint64_t total[kMaxPackCols];  // the fold of all pieces of the last group
+  int has_carry = 0, has_total = 0;     // the first group began earlier / the last group runs on
+  int64_t carry_rows = 0, total_rows = 0;
+};
+// fwd [n_chan][n]: a forward window_scan whose channels 0 and 1 are GROUP_HEAD
+// and PEER_HEAD; rev [2][n]: a reverse scan of those two. One elementwise
+// launch: the carry applied (carry (+) value) to the rows of the first group,
+// the value taken at the row (ROWS), its last peer (RANGE) or the group's last
+// row (WHOLE; the total when the group runs on), decoded to the output column.
+void window_finish(const int64_t* fwd, const int64_t* rev, int64_t n, const WindowFinishSpec& spec, hipStream_t s);
+
 // ------------------------------------------------------------ data movement
 // dst[idx] = src[idx] over `dims`, both operands addressed by element strides
 // (src strides may be 0 or negative; pointers already include the offsets).

@@ -30,6 +30,7 @@ from .block import (Block, ObjectColumn, RaggedColumn, StringColumn, build_colum
                     is_dense)
 from .column import Column, compile_expressions
 from .column_info import ColumnInformation, DataFrameInfo, explain_schema
+from .window import WindowExpression, refuse_window_expression
 from .types import (ArrayType, BinaryType, BooleanType, DataType, DoubleType, FloatType, IntegerType,
                     LongType, NumericType, Row, StringType, StructField, StructType, scalar_type_of)
 
@@ -393,6 +394,8 @@ class DataFrame:
         field copied with all of its metadata. Computed expressions of one
         select run as ONE map_blocks over a generated graph."""
         names = [c for cs in cols for c in (cs if isinstance(cs, (list, tuple)) else [cs])]
+        if any(isinstance(n, WindowExpression) for n in names):
+            return self._select_windows(names)
         if any(isinstance(n, Column) for n in names):
             return self._select_columns(names)
         for n in names:
@@ -452,9 +455,51 @@ class DataFrame:
             base = core.map_blocks(fetches, self, feed_dict=feed)
         return base._project([(tmp[i] if src is None else src, name) for i, (name, src, _) in enumerate(outs)])
 
+    def _select_windows(self, items: Sequence[Any]) -> "DataFrame":
+        """select with window expressions (frame/window.py) next to names and
+        plain column references."""
+        from .window import apply_windows
+        outs: List[tuple] = []  # (output name, source column or the window expression)
+        for it in items:
+            if isinstance(it, WindowExpression):
+                if not it.has_alias:
+                    raise ValueError(f"select: the window expression '{it.output_name}' needs a name; give it an "
+                                     f".alias()")
+                outs.append((it.output_name, it))
+                continue
+            if isinstance(it, str):
+                it = Column._ref(it)
+            elif not isinstance(it, Column):
+                raise TypeError(f"select: a column name, a Column or a window expression is expected, got "
+                                f"{type(it).__name__}")
+            it._no_sort_order("select")
+            if not it.is_reference:
+                raise TypeError(f"select: the computed Column '{it.output_name}' stands next to a window expression; "
+                                f"split the call: add the window columns first (select or withColumn), then "
+                                f"compute with them")
+            if it._expr[1] not in self._schema:
+                raise ValueError(f"Column {it._expr[1]} not found in {self.columns}")
+            outs.append((it.output_name, it._expr[1]))
+        seen = set()
+        for name, _ in outs:
+            if name in seen:
+                raise ValueError(f"select: duplicate output column name '{name}'; give one of them an .alias()")
+            seen.add(name)
+        return apply_windows(self, outs, "select")
+
     def withColumn(self, name: str, expr: Column) -> "DataFrame":  # noqa: N802
         """Appends column `name`; an existing column of that name is replaced
-        in place (keeps its position), as in Spark."""
+        in place (keeps its position), as in Spark. `expr` is a Column or a
+        window expression (`F.row_number().over(w)`, `F.sum("x").over(w)`);
+        the latter gives the rows in the window's sort order."""
+        if isinstance(expr, WindowExpression):
+            from .window import apply_windows
+            if not isinstance(name, str) or not name:
+                raise TypeError(f"withColumn: a non-empty column name is expected, got {name!r}")
+            outs = [(c, expr if c == name else c) for c in self.columns]
+            if name not in self._schema:
+                outs.append((name, expr))
+            return apply_windows(self, outs, "withColumn")
         if not isinstance(expr, Column):
             raise TypeError(f"withColumn: a Column expression is expected, got {type(expr).__name__}")
         expr._no_sort_order("withColumn")
@@ -484,6 +529,7 @@ class DataFrame:
         device by the row-compaction kernels (kernels/compact.hip); of a host
         partition only the predicate's inputs travel to the GPU and only the
         mask comes back."""
+        refuse_window_expression("filter", [cond])
         if not isinstance(cond, Column):
             raise TypeError(f"filter: a boolean Column is expected (e.g. df.x > 3), got {type(cond).__name__}")
         cond._no_sort_order("filter")
@@ -994,6 +1040,7 @@ def _sort_frame(df: DataFrame, cols: Sequence[Any], ascending, global_order: boo
     from .. import core
     from ..utils.logging import metrics
     items = [c for cs in cols for c in (cs if isinstance(cs, (list, tuple)) else [cs])]
+    refuse_window_expression(what, items)
     if not items:
         raise ValueError(f"{what}: at least one sort key is expected")
     if len(items) > _MAX_SORT_KEYS:

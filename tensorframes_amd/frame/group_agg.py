@@ -55,6 +55,8 @@ def _tf_dtype(df, name: str) -> int:
 
 
 def _specs(df, keys: Sequence[str], exprs: Sequence[Any], what: str) -> List[_Spec]:
+    from .window import refuse_window_expression
+    refuse_window_expression(what, exprs)
     if len(exprs) == 1 and isinstance(exprs[0], dict):
         made = []
         for col, fn in exprs[0].items():

@@ -15,7 +15,7 @@ from typing import Optional
 from .frame.column import Column
 
 __all__ = ["AggregateExpression", "count", "sum", "avg", "mean", "min", "max", "stddev", "stddev_samp", "stddev_pop",
-           "variance", "var_samp", "var_pop"]
+           "variance", "var_samp", "var_pop", "row_number", "rank", "dense_rank"]
 
 # the canonical statistic behind every accepted name (the dict form of agg uses the same table)
 FUNCTIONS = {
@@ -49,8 +49,35 @@ class AggregateExpression:
             return self._alias
         return f"{self.fn}({self.column if self.column is not None else 1})"
 
+    def over(self, spec):
+        """This aggregate over the rows of a window (`Window.partitionBy(...)`
+        ...): one value per row, for `DataFrame.withColumn` / `select`. count,
+        sum, avg / mean, min and max; the output types are those of
+        `groupBy().agg`."""
+        from .frame.window import _AGGREGATES, WindowExpression
+        if self.fn not in _AGGREGATES:
+            raise NotImplementedError(f"{self.fn}({self.column}).over: {self.fn} is not supported over a window; "
+                                      f"count, sum, avg, min and max are")
+        return WindowExpression(self.fn, self.column, spec, self._alias)
+
     def __repr__(self):
         return f"AggregateExpression<{self.output_name}>"
+
+
+class RankingFunction:
+    """`row_number()`, `rank()` or `dense_rank()` before its `.over(spec)`."""
+
+    __slots__ = ("fn",)
+
+    def __init__(self, fn: str):
+        self.fn = fn
+
+    def over(self, spec):
+        from .frame.window import WindowExpression
+        return WindowExpression(self.fn, None, spec)
+
+    def __repr__(self):
+        return f"RankingFunction<{self.fn}()>"
 
 
 def _make(fn: str, col) -> AggregateExpression:
@@ -123,3 +150,20 @@ def var_samp(col) -> AggregateExpression:
 
 def var_pop(col) -> AggregateExpression:
     return _make("var_pop", col)
+
+
+def row_number() -> RankingFunction:
+    """1, 2, 3, ... within the group, in the spec's order (int32); ties keep
+    the input's order."""
+    return RankingFunction("row_number")
+
+
+def rank() -> RankingFunction:
+    """The row number of the first of the row's peers (rows whose order keys
+    tie): 1, 1, 3, ... (int32)."""
+    return RankingFunction("rank")
+
+
+def dense_rank() -> RankingFunction:
+    """Distinct order-key tuples of the group up to the row's: 1, 1, 2, ... (int32)."""
+    return RankingFunction("dense_rank")
