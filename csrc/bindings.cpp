@@ -129,6 +129,54 @@ at::Tensor host_key_from_image(const at::Tensor& img, at::ScalarType st) {
   return st == at::kDouble ? key_from_image_typed<double, int64_t>(img, st) : key_from_image_typed<float, int32_t>(img, st);
 }
 
+// the position of s in names, -1 when it is none of them
+template <size_t N>
+int name_index(const char* const (&names)[N], const std::string& s) {
+  for (size_t i = 0; i < N; ++i)
+    if (s == names[i]) return static_cast<int>(i);
+  return -1;
+}
+
+// st is one of the seven statistics dtypes, or a type_error "<subject><st><object>, which is not supported (...)"
+void require_stat_type(at::ScalarType st, const std::string& subject, const char* object) {
+  if (st != at::kFloat && st != at::kDouble && st != at::kLong && st != at::kInt && st != at::kShort &&
+      st != at::kChar && st != at::kByte)
+    throw py::type_error(str_cat(subject, c10::toString(st), object, ", which is not supported (uint8, int8, int16, "
+                                 "int32, int64, float32 or float64)"));
+}
+
+// a dense scalar column of one of the seven statistics dtypes, or the typed error
+void stat_column(const char* what, const at::Tensor& t, const std::string& which) {
+  if (!t.is_cuda()) throw py::value_error(str_cat(what, ": ", which, " must be a device tensor"));
+  if (t.dim() != 1) throw py::value_error(str_cat(what, ": ", which, " must be 1-D (one scalar per row)"));
+  require_stat_type(t.scalar_type(), str_cat(what, ": ", which, " is "), "");
+  if (!t.is_contiguous())
+    throw py::value_error(str_cat(what, ": ", which, " is not contiguous; make it contiguous first"));
+}
+
+// stat_column on the device and with the row count of `like` (ref names it in the errors)
+void stat_column_like(const char* what, const at::Tensor& t, const std::string& which, const char* ref,
+                      const at::Device& dev, int64_t n, DType* dtype, const void** ptr) {
+  stat_column(what, t, which);
+  if (t.device() != dev) throw py::value_error(str_cat(what, ": ", which, " is not on ", ref, "'s device"));
+  if (t.size(0) != n) throw py::value_error(str_cat(what, ": ", which, " has ", t.size(0), " rows, ", ref, " ", n));
+  *dtype = from_scalar_type(t.scalar_type());
+  *ptr = t.data_ptr();
+}
+
+// 1..kMaxPackCols columns as on cols[0]'s device and with its row count
+k::StatCols stat_cols_from(const char* what, const std::vector<at::Tensor>& cols) {
+  if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
+    throw py::value_error(str_cat(what, ": 1..", k::kMaxPackCols, " columns per call, got ", cols.size()));
+  k::StatCols sc;
+  sc.n = static_cast<int>(cols.size());
+  stat_column(what, cols[0], "column 0");  // (before its row count is read)
+  for (size_t c = 0; c < cols.size(); ++c)
+    stat_column_like(what, cols[c], str_cat("column ", c), "the first column", cols[0].device(), cols[0].size(0),
+                     &sc.dtype[c], &sc.ptr[c]);
+  return sc;
+}
+
 }  // namespace
 
 namespace tfa {
@@ -954,34 +1002,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "order, a row's matches in sorted (= build row) order; one stream synchronisation reads the total");
   // DataFrame.describe / summary / approxQuantile on device-resident columns (kernels/stats.hip)
   m.def("stats_tile_rows", [] { return k::stats_tile_rows(); }, "rows per tile of select_hist");
-  // a dense scalar column of one of the seven statistics dtypes, or the typed error
-  auto stat_column = [](const char* what, const at::Tensor& t, const std::string& which) {
-    if (!t.is_cuda()) throw py::value_error(str_cat(what, ": ", which, " must be a device tensor"));
-    if (t.dim() != 1) throw py::value_error(str_cat(what, ": ", which, " must be 1-D (one scalar per row)"));
-    const auto st = t.scalar_type();
-    if (st != at::kFloat && st != at::kDouble && st != at::kLong && st != at::kInt && st != at::kShort &&
-        st != at::kChar && st != at::kByte)
-      throw py::type_error(str_cat(what, ": ", which, " is ", c10::toString(st), ", which is not supported (uint8, "
-                                   "int8, int16, int32, int64, float32 or float64)"));
-    if (!t.is_contiguous())
-      throw py::value_error(str_cat(what, ": ", which, " is not contiguous; make it contiguous first"));
-  };
-  m.def("column_moments", [stat_column](const std::vector<at::Tensor>& cols) {
-    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
-      throw py::value_error(str_cat("column_moments: 1..", k::kMaxPackCols, " columns per call, got ", cols.size()));
-    k::StatCols sc;
-    sc.n = static_cast<int>(cols.size());
-    for (size_t c = 0; c < cols.size(); ++c) {
-      const at::Tensor& t = cols[c];
-      stat_column("column_moments", t, str_cat("column ", c));
-      if (t.device() != cols[0].device())
-        throw py::value_error(str_cat("column_moments: column ", c, " is not on the first column's device"));
-      if (t.size(0) != cols[0].size(0))
-        throw py::value_error(str_cat("column_moments: column ", c, " has ", t.size(0), " rows, the first column ",
-                                      cols[0].size(0)));
-      sc.dtype[c] = from_scalar_type(t.scalar_type());
-      sc.ptr[c] = t.data_ptr();
-    }
+  m.def("column_moments", [](const std::vector<at::Tensor>& cols) {
+    const k::StatCols sc = stat_cols_from("column_moments", cols);
     const int64_t n = cols[0].size(0), C = sc.n;
     const auto dev = cols[0].device();
     if (n == 0) {  // nothing is launched
@@ -1007,7 +1029,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "up to 16 dense scalar device columns [n] (mixed dtypes, contiguous) -> (moments f64 [C, 3]: n, mean, M2 = the "
      "sum of squared deviations; extremes int64 [C, 2]: the smallest and largest order-preserving word, bit "
      "patterns), device tensors; the same bits on every run. n == 0 gives (0, NaN, NaN) and (all ones, 0)");
-  m.def("select_hist", [stat_column](const at::Tensor& col, const at::Tensor& prefixes0, int prefix_bits) {
+  m.def("select_hist", [](const at::Tensor& col, const at::Tensor& prefixes0, int prefix_bits) {
     stat_column("select_hist", col, "the column");
     if (prefixes0.scalar_type() != at::kLong || prefixes0.dim() != 1)
       throw py::value_error("select_hist: int64 prefixes [P] expected");
@@ -1049,23 +1071,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     if (t.dim() != 1) throw py::value_error(str_cat(what, ": ", which, " must be 1-D"));
     if (!t.is_contiguous()) throw py::value_error(str_cat(what, ": ", which, " is not contiguous"));
   };
-  m.def("group_moments", [stat_column, group_index](const std::vector<at::Tensor>& cols, const at::Tensor& perm,
-                                                    const at::Tensor& offsets) {
-    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
-      throw py::value_error(str_cat("group_moments: 1..", k::kMaxPackCols, " columns per call, got ", cols.size()));
-    k::StatCols sc;
-    sc.n = static_cast<int>(cols.size());
-    for (size_t c = 0; c < cols.size(); ++c) {
-      const at::Tensor& t = cols[c];
-      stat_column("group_moments", t, str_cat("column ", c));
-      if (t.device() != cols[0].device())
-        throw py::value_error(str_cat("group_moments: column ", c, " is not on the first column's device"));
-      if (t.size(0) != cols[0].size(0))
-        throw py::value_error(str_cat("group_moments: column ", c, " has ", t.size(0), " rows, the first column ",
-                                      cols[0].size(0)));
-      sc.dtype[c] = from_scalar_type(t.scalar_type());
-      sc.ptr[c] = t.data_ptr();
-    }
+  m.def("group_moments", [group_index](const std::vector<at::Tensor>& cols, const at::Tensor& perm,
+                                       const at::Tensor& offsets) {
+    const k::StatCols sc = stat_cols_from("group_moments", cols);
     const auto dev = cols[0].device();
     group_index("group_moments", "perm", perm, dev);
     group_index("group_moments", "offsets", offsets, dev);
@@ -1135,15 +1143,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     for (size_t o = 0; o < cols.size(); ++o) {
       if (cols[o] < 0 || cols[o] >= C)
         throw py::value_error(str_cat("group_results: output ", o, " names column ", cols[o], " of ", C));
-      int st = -1;
-      for (int i = 0; i < 9; ++i)
-        if (stats[o] == names[i]) st = i;
+      const int st = name_index(names, stats[o]);
       if (st < 0) throw py::value_error(str_cat("group_results: '", stats[o], "' is not a statistic"));
       const at::ScalarType ct = dtypes[o];
-      if (ct != at::kFloat && ct != at::kDouble && ct != at::kLong && ct != at::kInt && ct != at::kShort &&
-          ct != at::kChar && ct != at::kByte)
-        throw py::type_error(str_cat("group_results: output ", o, " reads a ", c10::toString(ct), " column, which is "
-                                     "not supported (uint8, int8, int16, int32, int64, float32 or float64)"));
+      require_stat_type(ct, str_cat("group_results: output ", o, " reads a "), " column");
       const bool fl = ct == at::kFloat || ct == at::kDouble;
       const auto gs = static_cast<k::GroupStat>(st);
       at::ScalarType ot = at::kDouble;
@@ -1173,9 +1176,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     if (t.dim() != 2) throw py::value_error(str_cat(what, ": ", which, " must be 2-D [*, n]"));
     if (!t.is_contiguous()) throw py::value_error(str_cat(what, ": ", which, " is not contiguous"));
   };
-  m.def("window_scan", [stat_column, window_table](const at::Tensor& words, int64_t P, bool reverse,
-                                                   const std::vector<std::string>& kinds,
-                                                   const std::vector<at::Tensor>& cols) {
+  m.def("window_scan", [window_table](const at::Tensor& words, int64_t P, bool reverse,
+                                      const std::vector<std::string>& kinds, const std::vector<at::Tensor>& cols) {
     static const char* const names[] = {"group_head", "peer_head", "peer_count", "sum_i64", "sum_f64", "min_word",
                                         "max_word"};
     window_table("window_scan", "the words", words);
@@ -1189,9 +1191,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     ch.n = static_cast<int>(kinds.size());
     size_t used = 0;
     for (size_t c = 0; c < kinds.size(); ++c) {
-      int kd = -1;
-      for (int i = 0; i < 7; ++i)
-        if (kinds[c] == names[i]) kd = i;
+      const int kd = name_index(names, kinds[c]);
       if (kd < 0) throw py::value_error(str_cat("window_scan: '", kinds[c], "' is not a channel kind"));
       ch.kind[c] = kd;
       ch.dtype[c] = DType::U8;
@@ -1199,15 +1199,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       if (kd < static_cast<int>(k::WindowChan::SUM_I64)) continue;
       if (used >= cols.size())
         throw py::value_error(str_cat("window_scan: channel ", c, " (", kinds[c], ") has no value column"));
-      const at::Tensor& t = cols[used++];
-      stat_column("window_scan", t, str_cat("the column of channel ", c));
-      if (t.device() != words.device())
-        throw py::value_error(str_cat("window_scan: the column of channel ", c, " is not on the words' device"));
-      if (t.size(0) != n)
-        throw py::value_error(str_cat("window_scan: the column of channel ", c, " has ", t.size(0),
-                                      " rows, the words ", n));
-      ch.dtype[c] = from_scalar_type(t.scalar_type());
-      ch.ptr[c] = t.data_ptr();
+      stat_column_like("window_scan", cols[used++], str_cat("the column of channel ", c), "the words", words.device(), n,
+                       &ch.dtype[c], &ch.ptr[c]);
     }
     if (used != cols.size())
       throw py::value_error(str_cat("window_scan: ", cols.size(), " value columns for ", used, " value channels"));
@@ -1258,8 +1251,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     sp.n_chan = static_cast<int>(C);
     std::vector<int> kd(C, -1);
     for (int64_t c = 0; c < C; ++c) {
-      for (int i = 0; i < 7; ++i)
-        if (kinds[c] == kind_names[i]) kd[c] = i;
+      kd[c] = name_index(kind_names, kinds[c]);
       if (kd[c] < 0) throw py::value_error(str_cat("window_finish: '", kinds[c], "' is not a channel kind"));
       sp.op[c] = k::window_chan_op(kd[c]);
       sp.carry[c] = static_cast<uint64_t>(carry[c]);
@@ -1275,20 +1267,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     c10::hip::HIPGuard guard(fwd.device().index());
     std::vector<at::Tensor> outs;
     for (size_t o = 0; o < fns.size(); ++o) {
-      int fn = -1, fr = -1;
-      for (int i = 0; i < 8; ++i)
-        if (fns[o] == fn_names[i]) fn = i;
-      for (int i = 0; i < 3; ++i)
-        if (frames[o] == frame_names[i]) fr = i;
+      const int fn = name_index(fn_names, fns[o]), fr = name_index(frame_names, frames[o]);
       if (fn < 0) throw py::value_error(str_cat("window_finish: '", fns[o], "' is not a window function"));
       if (fr < 0) throw py::value_error(str_cat("window_finish: '", frames[o], "' is not a frame"));
       if (chans[o] < 0 || chans[o] >= C)
         throw py::value_error(str_cat("window_finish: output ", o, " names channel ", chans[o], " of ", C));
       const at::ScalarType ct = dtypes[o];
-      if (ct != at::kFloat && ct != at::kDouble && ct != at::kLong && ct != at::kInt && ct != at::kShort &&
-          ct != at::kChar && ct != at::kByte)
-        throw py::type_error(str_cat("window_finish: output ", o, " reads a ", c10::toString(ct), " column, which "
-                                     "is not supported (uint8, int8, int16, int32, int64, float32 or float64)"));
+      require_stat_type(ct, str_cat("window_finish: output ", o, " reads a "), " column");
       const auto wf = static_cast<k::WindowFn>(fn);
       const int ck = kd[chans[o]];
       at::ScalarType ot = at::kInt;

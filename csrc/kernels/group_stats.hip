@@ -39,7 +39,9 @@
 #include <cmath>
 #include <limits>
 
+#include "column_types.h"
 #include "hip_common.h"
+#include "moments.h"
 #include "sort_words.h"
 
 namespace tfa {
@@ -61,37 +63,22 @@ static_assert(sizeof(GRec) == 8 * kGroupRecordFields, "a record is six 8-byte fi
 
 __device__ __forceinline__ GRec grec_empty() { return GRec{0.0, 0.0, 0.0, 0ull, ~0ull, 0ull}; }
 
-__device__ __forceinline__ uint64_t f64_bits(double x) { return static_cast<uint64_t>(__double_as_longlong(x)); }
-__device__ __forceinline__ double bits_f64(uint64_t b) { return __longlong_as_double(static_cast<long long>(b)); }
+// the sum field in moments.h's merge and shuffle: wrapping for the integer
+// dtypes, f64 for the float ones (an empty side selected away, as the mean)
+struct SumField {
+  bool is_float;
+  __device__ __forceinline__ void merge(GRec& r, const GRec& a, const GRec& b) const {
+    r.sum = is_float ? (a.n == 0.0 ? b.sum : (b.n == 0.0 ? a.sum : f64_bits(bits_f64(a.sum) + bits_f64(b.sum))))
+                     : a.sum + b.sum;
+  }
+  __device__ __forceinline__ void shfl_xor(GRec& o, const GRec& r, int off) const {
+    o.sum = __shfl_xor(static_cast<unsigned long long>(r.sum), off, kWave);
+  }
+};
 
-// Chan's merge of two records, `a` the earlier rows (the arithmetic of
-// stats.hip's rec_merge, plus the sum)
 __device__ __forceinline__ GRec grec_merge(const GRec& a, const GRec& b, bool is_float) {
-  GRec r;
-  r.n = a.n + b.n;
-  const double delta = b.mean - a.mean;
-  const double f = r.n > 0.0 ? b.n / r.n : 0.0;
-  r.mean = a.n == 0.0 ? b.mean : (b.n == 0.0 ? a.mean : a.mean + delta * f);
-  r.m2 = a.n == 0.0 ? b.m2 : (b.n == 0.0 ? a.m2 : a.m2 + b.m2 + delta * delta * (a.n * f));
-  r.sum = is_float ? (a.n == 0.0 ? b.sum : (b.n == 0.0 ? a.sum : f64_bits(bits_f64(a.sum) + bits_f64(b.sum))))
-                   : a.sum + b.sum;
-  r.lo = a.lo < b.lo ? a.lo : b.lo;
-  r.hi = a.hi > b.hi ? a.hi : b.hi;
-  return r;
+  return merge_moments(a, b, SumField{is_float});
 }
-
-__device__ __forceinline__ GRec grec_shfl_xor(const GRec& r, int off) {
-  GRec o;
-  o.n = __shfl_xor(r.n, off, kWave);
-  o.mean = __shfl_xor(r.mean, off, kWave);
-  o.m2 = __shfl_xor(r.m2, off, kWave);
-  o.sum = __shfl_xor(static_cast<unsigned long long>(r.sum), off, kWave);
-  o.lo = __shfl_xor(static_cast<unsigned long long>(r.lo), off, kWave);
-  o.hi = __shfl_xor(static_cast<unsigned long long>(r.hi), off, kWave);
-  return o;
-}
-
-__device__ __forceinline__ bool float_dtype(DType d) { return d == DType::F32 || d == DType::F64; }
 
 template <typename T>
 struct SumOf {  // integers: wrapping 64-bit; floats: f64
@@ -149,18 +136,6 @@ __device__ __forceinline__ GRec lane_rows(const void* __restrict__ src, const in
   return out;
 }
 
-// the last i in [a, b] with p[i] <= j (p[a] <= j is given)
-__device__ __forceinline__ int64_t last_not_above(const int64_t* __restrict__ p, int64_t a, int64_t b, int64_t j) {
-  while (a < b) {
-    const int64_t mid = a + (b - a + 1) / 2;
-    if (p[mid] <= j) a = mid;
-    else b = mid - 1;
-  }
-  return a;
-}
-
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ __forceinline__ void store_rec(int64_t* __restrict__ dst, const GRec& r) {
   dst[0] = static_cast<int64_t>(f64_bits(r.n));
   dst[1] = static_cast<int64_t>(f64_bits(r.mean));
@@ -205,33 +180,17 @@ __global__ __launch_bounds__(kT) void group_moments_kernel(StatCols cols, int64_
                        __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x / kWave));
   if (item >= items) return;  // (the whole wave)
   // coffs[0] == 0 <= item < coffs[nseg]: the segment lies in [0, nseg - 1]
-  const int64_t g = last_not_above(coffs, 0, nseg - 1, item);
+  const int64_t g = last_not_above(coffs, 0, 0, nseg - 1, item);
   const int64_t ch = item - coffs[g];
   const int64_t a = clamp64(offsets[g], 0, nperm), b = clamp64(offsets[g + 1], a, nperm);
   const int64_t lo = clamp64(a + ch * kGroupChunk, a, b);
   const int64_t hi = lo + kGroupChunk < b ? lo + kGroupChunk : b;
   const void* src = cols.ptr[c];
   const DType dt = cols.dtype[c];
-  GRec r;
-  switch (dt) {  // (uniform: one scalar branch per block)
-    case DType::F32: r = lane_rows<float>(src, perm, lo, hi, n, lane); break;
-    case DType::F64: r = lane_rows<double>(src, perm, lo, hi, n, lane); break;
-    case DType::I64: r = lane_rows<int64_t>(src, perm, lo, hi, n, lane); break;
-    case DType::I32: r = lane_rows<int32_t>(src, perm, lo, hi, n, lane); break;
-    case DType::I16: r = lane_rows<int16_t>(src, perm, lo, hi, n, lane); break;
-    case DType::I8: r = lane_rows<int8_t>(src, perm, lo, hi, n, lane); break;
-    default: r = lane_rows<uint8_t>(src, perm, lo, hi, n, lane); break;  // U8
-  }
-  const bool fl = float_dtype(dt);
-  const int64_t rows = hi - lo;  // (the same in every lane)
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {  // lane order: neighbours first
-    // lanes from `rows` on hold empty records, and merging an empty record
-    // changes no bit: a short chunk stops early (a one-row group merges nothing)
-    if (off >= rows) break;
-    const GRec o = grec_shfl_xor(r, off);
-    r = (lane & off) ? grec_merge(o, r, fl) : grec_merge(r, o, fl);
-  }
+  // (the dtype is uniform: one scalar branch per block)
+  GRec r = dispatch_column(dt, [&](auto tag) { return lane_rows<decltype(tag)>(src, perm, lo, hi, n, lane); });
+  // a short chunk stops early (a one-row group merges nothing)
+  r = wave_merge_moments(r, SumField{is_float_dtype(dt)}, hi - lo);
   if (lane == 0) store_rec(part + (item * gridDim.y + c) * kGroupRecordFields, r);
 }
 
@@ -253,7 +212,7 @@ __global__ __launch_bounds__(kT) void group_fold_kernel(StatCols cols, const int
   const int64_t a = clamp64(coffs[g], 0, items - 1), b = clamp64(coffs[g + 1], a + 1, items);
   const bool wide = valid && b - a > kFoldSerial;
   if (valid && !wide) {
-    const bool fl = float_dtype(cols.dtype[c]);
+    const bool fl = is_float_dtype(cols.dtype[c]);
     GRec r = load_rec(part + (a * C + c) * kGroupRecordFields);
     for (int64_t i = a + 1; i < b; ++i) r = grec_merge(r, load_rec(part + (i * C + c) * kGroupRecordFields), fl);
     store_rec(out + t * kGroupRecordFields, r);
@@ -265,16 +224,20 @@ __global__ __launch_bounds__(kT) void group_fold_kernel(StatCols cols, const int
     const int64_t sa = __shfl(static_cast<long long>(a), src, kWave), sb = __shfl(static_cast<long long>(b), src, kWave);
     const int64_t st = __shfl(static_cast<long long>(t), src, kWave);
     const int sc = __shfl(c, src, kWave);
-    const bool fl = float_dtype(cols.dtype[sc]);
+    const bool fl = is_float_dtype(cols.dtype[sc]);
     const int64_t per = (sb - sa + kWave - 1) / kWave;
     const int64_t i0 = sa + lane * per < sb ? sa + lane * per : sb, i1 = i0 + per < sb ? i0 + per : sb;
     GRec r = grec_empty();
     if (i0 < i1) r = load_rec(part + (i0 * C + sc) * kGroupRecordFields);
     for (int64_t i = i0 + 1; i < i1; ++i) r = grec_merge(r, load_rec(part + (i * C + sc) * kGroupRecordFields), fl);
+    // wave_merge_moments written out: through the helper the compiler schedules
+    // this loop nest differently (same registers), and the skewed case of
+    // scripts/group_agg_profile.py then measured 0.3 % outside its run-to-run spread
+    const SumField sum{fl};
 #pragma unroll
     for (int off = 1; off < kWave; off <<= 1) {
-      const GRec o = grec_shfl_xor(r, off);
-      r = (lane & off) ? grec_merge(o, r, fl) : grec_merge(r, o, fl);
+      const GRec o = shfl_xor_moments(r, off, sum);
+      r = (lane & off) ? merge_moments(o, r, sum) : merge_moments(r, o, sum);
     }
     if (lane == 0) store_rec(out + st * kGroupRecordFields, r);
   }
@@ -325,18 +288,10 @@ __global__ __launch_bounds__(kT) void group_results_kernel(const int64_t* __rest
   if (st == GroupStat::MIN || st == GroupStat::MAX) {
     const bool has = r.n > 0.0;  // (a group without rows has no extreme: zero)
     const uint64_t w = st == GroupStat::MIN ? r.lo : r.hi;
-    switch (dt) {
-      case DType::F32: static_cast<uint32_t*>(out)[g] = has ? decode_f32(w) : 0u; break;
-      case DType::F64: static_cast<uint64_t*>(out)[g] = has ? decode_f64(w) : 0ull; break;
-      case DType::I64: static_cast<int64_t*>(out)[g] = has ? decode_int(w) : 0; break;
-      case DType::I32: static_cast<int32_t*>(out)[g] = has ? static_cast<int32_t>(decode_int(w)) : 0; break;
-      case DType::I16: static_cast<int16_t*>(out)[g] = has ? static_cast<int16_t>(decode_int(w)) : 0; break;
-      case DType::I8: static_cast<int8_t*>(out)[g] = has ? static_cast<int8_t>(decode_int(w)) : 0; break;
-      default: static_cast<uint8_t*>(out)[g] = has ? static_cast<uint8_t>(w) : 0; break;  // U8
-    }
+    store_word(out, g, dt, w, has);
     return;
   }
-  const bool fl = float_dtype(dt);
+  const bool fl = is_float_dtype(dt);
   if (st == GroupStat::SUM && !fl) {
     static_cast<int64_t*>(out)[g] = static_cast<int64_t>(r.sum);
     return;
@@ -370,11 +325,6 @@ __global__ __launch_bounds__(kT) void group_results_kernel(const int64_t* __rest
 // ------------------------------------------------------------------ host API
 namespace {
 
-bool group_stat_dtype(DType d) {
-  return d == DType::F32 || d == DType::F64 || d == DType::I64 || d == DType::I32 || d == DType::I16 ||
-         d == DType::I8 || d == DType::U8;
-}
-
 int64_t max_chunks(int64_t nperm) { return std::max<int64_t>(1, (nperm + kGroupChunk - 1) / kGroupChunk); }
 
 size_t align8(size_t b) { return (b + 7) & ~size_t(7); }
@@ -395,12 +345,7 @@ void group_moments(const StatCols& cols, int64_t n, const int64_t* perm, int64_t
                    int64_t nseg, int64_t* records, void* ws, size_t ws_size, hipStream_t s) {
   TFA_CHECK(cols.n >= 1 && cols.n <= kMaxPackCols, "group_moments: 1..", kMaxPackCols, " columns, got ", cols.n);
   TFA_CHECK(n >= 0 && nperm >= 0 && nperm <= n && nseg >= 0, "group_moments: bad row or segment count");
-  for (int c = 0; c < cols.n; ++c) {
-    TFA_CHECK(group_stat_dtype(cols.dtype[c]), "group_moments: column ", c, " has a dtype that is not supported");
-    TFA_CHECK(n == 0 || cols.ptr[c] != nullptr, "group_moments: column ", c, " has no data");
-    TFA_CHECK(reinterpret_cast<uintptr_t>(cols.ptr[c]) % static_cast<uintptr_t>(dtype_size(cols.dtype[c])) == 0,
-              "group_moments: column ", c, " is not aligned to its element size");
-  }
+  check_stat_columns("group_moments", cols, n);
   if (n == 0 || nseg == 0) return;
   TFA_CHECK(nseg < (int64_t(1) << 31) && nseg + max_chunks(nperm) < (int64_t(1) << 31),
             "group_moments: too many segments");
@@ -452,7 +397,7 @@ void group_results(const int64_t* records, int64_t ng, int ncols, const GroupRes
   for (int o = 0; o < spec.n; ++o) {
     TFA_CHECK(spec.col[o] >= 0 && spec.col[o] < ncols, "group_results: output ", o, " names column ", spec.col[o],
               " of ", ncols);
-    TFA_CHECK(group_stat_dtype(spec.dtype[o]), "group_results: output ", o, " has a dtype that is not supported");
+    TFA_CHECK(is_stat_dtype(spec.dtype[o]), "group_results: output ", o, " has a dtype that is not supported");
     TFA_CHECK(static_cast<int>(spec.stat[o]) >= 0 && static_cast<int>(spec.stat[o]) <= static_cast<int>(GroupStat::STDDEV_POP),
               "group_results: output ", o, " asks for an unknown statistic");
     TFA_CHECK(ng == 0 || spec.out[o] != nullptr, "group_results: output ", o, " has no buffer");

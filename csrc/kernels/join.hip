@@ -27,6 +27,7 @@
 // Row counts, positions and offsets are 64-bit.
 #include <algorithm>
 
+#include "column_types.h"
 #include "hip_common.h"
 
 namespace tfa {
@@ -198,20 +199,6 @@ __global__ __launch_bounds__(kJT) void join_tile_scan_kernel(const int64_t* __re
     run += c[j];
   }
 }
-
-namespace {
-
-// the last i in [a, b] with p[i - base] <= j (p[a - base] <= j is given)
-__device__ __forceinline__ int64_t last_not_above(const int64_t* p, int64_t base, int64_t a, int64_t b, int64_t j) {
-  while (a < b) {
-    const int64_t mid = a + (b - a + 1) / 2;
-    if (p[mid - base] <= j) a = mid;
-    else b = mid - 1;
-  }
-  return a;
-}
-
-}  // namespace
 
 // block b: output rows [b * kJoinTile, min(total, (b + 1) * kJoinTile)).
 // offs [n + 1] with offs[n] == total; lo [n]; perm [m]

@@ -1,6 +1,7 @@
 // The order-preserving 64-bit word of one scalar (the table in kernels.h, sort
-// section; ascending): the one definition that sort.hip and stats.hip encode
-// with.
+// section; ascending): the one definition that sort.hip, stats.hip,
+// group_stats.hip and window_scan.hip encode with, and that column_types.h
+// decodes with.
 #pragma once
 
 #include <cstdint>

@@ -26,7 +26,9 @@
 #include <cmath>
 #include <limits>
 
+#include "column_types.h"
 #include "hip_common.h"
+#include "moments.h"
 #include "radix.h"
 #include "sort_words.h"
 
@@ -48,44 +50,16 @@ struct Rec {
 
 __device__ __forceinline__ Rec rec_empty() { return Rec{0.0, 0.0, 0.0, ~0ull, 0ull}; }
 
-// Chan's merge of two records, `a` the earlier rows
-__device__ __forceinline__ Rec rec_merge(const Rec& a, const Rec& b) {
-  Rec r;
-  r.n = a.n + b.n;
-  const double delta = b.mean - a.mean;
-  const double f = r.n > 0.0 ? b.n / r.n : 0.0;
-  // (an empty side holds mean 0: selected away, never mixed in)
-  r.mean = a.n == 0.0 ? b.mean : (b.n == 0.0 ? a.mean : a.mean + delta * f);
-  r.m2 = a.n == 0.0 ? b.m2 : (b.n == 0.0 ? a.m2 : a.m2 + b.m2 + delta * delta * (a.n * f));
-  r.lo = a.lo < b.lo ? a.lo : b.lo;
-  r.hi = a.hi > b.hi ? a.hi : b.hi;
-  return r;
-}
-
-__device__ __forceinline__ Rec rec_shfl_xor(const Rec& r, int off) {
-  Rec o;
-  o.n = __shfl_xor(r.n, off, kWave);
-  o.mean = __shfl_xor(r.mean, off, kWave);
-  o.m2 = __shfl_xor(r.m2, off, kWave);
-  o.lo = __shfl_xor(static_cast<unsigned long long>(r.lo), off, kWave);
-  o.hi = __shfl_xor(static_cast<unsigned long long>(r.hi), off, kWave);
-  return o;
-}
-
 // the block's record in thread 0: lanes in lane order (neighbours first), then
 // the waves in wave order
 __device__ __forceinline__ Rec block_merge(Rec r, Rec* lds /*[kWaves]*/) {
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const Rec o = rec_shfl_xor(r, off);
-    r = (lane & off) ? rec_merge(o, r) : rec_merge(r, o);
-  }
+  r = wave_merge_moments(r);
   if (lane == 0) lds[w] = r;
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int i = 1; i < kWaves; ++i) r = rec_merge(r, lds[i]);
+    for (int i = 1; i < kWaves; ++i) r = merge_moments(r, lds[i]);
   }
   return r;
 }
@@ -218,16 +192,8 @@ __global__ __launch_bounds__(kT) void moments_partial_kernel(StatCols cols, int6
   const int64_t lo = first < n ? first : n;
   const int64_t hi = lo + chunk < n ? lo + chunk : n;
   const void* src = cols.ptr[c];
-  Rec r;
-  switch (cols.dtype[c]) {  // (uniform: one scalar branch per block)
-    case DType::F32: r = lane_moments<float>(src, lo, hi); break;
-    case DType::F64: r = lane_moments<double>(src, lo, hi); break;
-    case DType::I64: r = lane_moments<int64_t>(src, lo, hi); break;
-    case DType::I32: r = lane_moments<int32_t>(src, lo, hi); break;
-    case DType::I16: r = lane_moments<int16_t>(src, lo, hi); break;
-    case DType::I8: r = lane_moments<int8_t>(src, lo, hi); break;
-    default: r = lane_moments<uint8_t>(src, lo, hi); break;  // U8
-  }
+  // (the dtype is uniform: one scalar branch per block)
+  Rec r = dispatch_column(cols.dtype[c], [&](auto tag) { return lane_moments<decltype(tag)>(src, lo, hi); });
   r = block_merge(r, lds);
   if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = r;
 }
@@ -242,7 +208,7 @@ __global__ __launch_bounds__(kT) void moments_final_kernel(const Rec* __restrict
   const int per = (nb + kT - 1) / kT;  // consecutive records per thread
   const int a = threadIdx.x * per, b = a + per < nb ? a + per : nb;
   Rec r = rec_empty();
-  for (int i = a; i < b; ++i) r = rec_merge(r, p[i]);
+  for (int i = a; i < b; ++i) r = merge_moments(r, p[i]);
   r = block_merge(r, lds);
   if (threadIdx.x == 0) {
     moments[3 * c] = r.n;
@@ -295,15 +261,7 @@ __global__ __launch_bounds__(kT) void select_hist_kernel(DType dtype, const void
   for (int i = threadIdx.x; i < kWaves * bins; i += kT) dyn[i] = 0;
   __syncthreads();
   uint32_t* h = dyn + (threadIdx.x / kWave) * bins;
-  switch (dtype) {  // (uniform)
-    case DType::F32: hist_column<float>(src, n, pre, P, prefix_bits, h); break;
-    case DType::F64: hist_column<double>(src, n, pre, P, prefix_bits, h); break;
-    case DType::I64: hist_column<int64_t>(src, n, pre, P, prefix_bits, h); break;
-    case DType::I32: hist_column<int32_t>(src, n, pre, P, prefix_bits, h); break;
-    case DType::I16: hist_column<int16_t>(src, n, pre, P, prefix_bits, h); break;
-    case DType::I8: hist_column<int8_t>(src, n, pre, P, prefix_bits, h); break;
-    default: hist_column<uint8_t>(src, n, pre, P, prefix_bits, h); break;  // U8
-  }
+  dispatch_column(dtype, [&](auto tag) { hist_column<decltype(tag)>(src, n, pre, P, prefix_bits, h); });  // (uniform)
   __syncthreads();
   for (int i = threadIdx.x; i < bins; i += kT) {
     uint32_t c = 0;
@@ -315,11 +273,6 @@ __global__ __launch_bounds__(kT) void select_hist_kernel(DType dtype, const void
 
 // ------------------------------------------------------------------ host API
 namespace {
-
-bool stat_dtype(DType d) {
-  return d == DType::F32 || d == DType::F64 || d == DType::I64 || d == DType::I32 || d == DType::I16 ||
-         d == DType::I8 || d == DType::U8;
-}
 
 // blocks per column and rows per block (a multiple of 16: blocks of an aligned
 // column start aligned)
@@ -348,12 +301,7 @@ void column_moments(const StatCols& cols, int64_t n, double* moments, int64_t* e
                     hipStream_t s) {
   TFA_CHECK(cols.n >= 1 && cols.n <= kMaxPackCols, "column_moments: 1..", kMaxPackCols, " columns, got ", cols.n);
   TFA_CHECK(n >= 0, "column_moments: negative row count");
-  for (int c = 0; c < cols.n; ++c) {
-    TFA_CHECK(stat_dtype(cols.dtype[c]), "column_moments: column ", c, " has a dtype that is not supported");
-    TFA_CHECK(n == 0 || cols.ptr[c] != nullptr, "column_moments: column ", c, " has no data");
-    TFA_CHECK(reinterpret_cast<uintptr_t>(cols.ptr[c]) % static_cast<uintptr_t>(dtype_size(cols.dtype[c])) == 0,
-              "column_moments: column ", c, " is not aligned to its element size");
-  }
+  check_stat_columns("column_moments", cols, n);
   if (n == 0) return;
   TFA_CHECK(moments != nullptr && extremes != nullptr && ws != nullptr, "column_moments: null buffer");
   TFA_CHECK(reinterpret_cast<uintptr_t>(moments) % 8 == 0 && reinterpret_cast<uintptr_t>(extremes) % 8 == 0 &&
@@ -371,7 +319,7 @@ void column_moments(const StatCols& cols, int64_t n, double* moments, int64_t* e
 
 void select_hist(DType dtype, const void* col, int64_t n, const int64_t* prefixes, int P, int prefix_bits,
                  int64_t* hist, hipStream_t s) {
-  TFA_CHECK(stat_dtype(dtype), "select_hist: the column has a dtype that is not supported");
+  TFA_CHECK(is_stat_dtype(dtype), "select_hist: the column has a dtype that is not supported");
   TFA_CHECK(P >= 1 && P <= kMaxPackCols, "select_hist: 1..", kMaxPackCols, " prefixes, got ", P);
   TFA_CHECK(prefix_bits >= 0 && prefix_bits <= 64 - radix::kBits && prefix_bits % radix::kBits == 0,
             "select_hist: prefix_bits must be one of 0, 8, ..., 56, got ", prefix_bits);

@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <limits>
 
+#include "column_types.h"
 #include "hip_common.h"
 #include "sort_words.h"
 
@@ -47,9 +48,6 @@ constexpr int kR = 8;  // consecutive rows per lane
 constexpr int kTile = kT * kR;
 
 enum : int { OP_ADD_I64 = 0, OP_ADD_F64 = 1, OP_MIN = 2, OP_MAX = 3 };
-
-__device__ __forceinline__ uint64_t f64_bits(double x) { return static_cast<uint64_t>(__double_as_longlong(x)); }
-__device__ __forceinline__ double bits_f64(uint64_t b) { return __longlong_as_double(static_cast<long long>(b)); }
 
 __host__ __device__ __forceinline__ int op_of(int kind) {
   switch (static_cast<WindowChan>(kind)) {
@@ -265,15 +263,7 @@ __device__ __forceinline__ void chan_inputs(const WindowChans& ch, int c, const 
   }
   const uint64_t idv = ident_rt(op_of(kind));
   const void* src = ch.ptr[c];
-  switch (ch.dtype[c]) {  // (uniform)
-    case DType::F32: load_vals<float>(src, m0, n, rev, kind, idv, x); break;
-    case DType::F64: load_vals<double>(src, m0, n, rev, kind, idv, x); break;
-    case DType::I64: load_vals<int64_t>(src, m0, n, rev, kind, idv, x); break;
-    case DType::I32: load_vals<int32_t>(src, m0, n, rev, kind, idv, x); break;
-    case DType::I16: load_vals<int16_t>(src, m0, n, rev, kind, idv, x); break;
-    case DType::I8: load_vals<int8_t>(src, m0, n, rev, kind, idv, x); break;
-    default: load_vals<uint8_t>(src, m0, n, rev, kind, idv, x); break;  // U8
-  }
+  dispatch_column(ch.dtype[c], [&](auto tag) { load_vals<decltype(tag)>(src, m0, n, rev, kind, idv, x); });  // (uniform)
 }
 
 }  // namespace
@@ -392,12 +382,6 @@ __global__ __launch_bounds__(kT) void window_tile_write_kernel(const int64_t* __
   }
 }
 
-namespace {
-
-__device__ __forceinline__ int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-}  // namespace
-
 // thread i of block (.., o): output o of row i
 __global__ __launch_bounds__(kT) void window_finish_kernel(const int64_t* __restrict__ fwd,
                                                            const int64_t* __restrict__ rev, int64_t n,
@@ -405,8 +389,8 @@ __global__ __launch_bounds__(kT) void window_finish_kernel(const int64_t* __rest
   const int o = blockIdx.y;
   const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
   if (i >= n) return;
-  const int64_t gh = clampi(fwd[i], 0, i), ph = clampi(fwd[n + i], gh, i);
-  const int64_t gl = clampi(rev[i], i, n - 1), pl = clampi(rev[n + i], i, gl);
+  const int64_t gh = clamp64(fwd[i], 0, i), ph = clamp64(fwd[n + i], gh, i);
+  const int64_t gl = clamp64(rev[i], i, n - 1), pl = clamp64(rev[n + i], i, gl);
   const bool first = sp.has_carry && gh == 0;             // the group began in an earlier partition
   const bool open = sp.has_total && gl == n - 1;          // the group runs on into a later one
   const int64_t before = first ? sp.carry_rows : 0;
@@ -441,27 +425,12 @@ __global__ __launch_bounds__(kT) void window_finish_kernel(const int64_t* __rest
     case WindowFn::DENSE_RANK: static_cast<int32_t*>(out)[i] = static_cast<int32_t>(v); break;
     case WindowFn::SUM: static_cast<uint64_t*>(out)[i] = v; break;  // (int64 or f64 bits: the channel's)
     case WindowFn::AVG: static_cast<double*>(out)[i] = bits_f64(v) / static_cast<double>(rows); break;
-    default:  // MIN, MAX: the word back to the column's type
-      switch (dt) {
-        case DType::F32: static_cast<uint32_t*>(out)[i] = decode_f32(v); break;
-        case DType::F64: static_cast<uint64_t*>(out)[i] = decode_f64(v); break;
-        case DType::I64: static_cast<int64_t*>(out)[i] = decode_int(v); break;
-        case DType::I32: static_cast<int32_t*>(out)[i] = static_cast<int32_t>(decode_int(v)); break;
-        case DType::I16: static_cast<int16_t*>(out)[i] = static_cast<int16_t>(decode_int(v)); break;
-        case DType::I8: static_cast<int8_t*>(out)[i] = static_cast<int8_t>(decode_int(v)); break;
-        default: static_cast<uint8_t*>(out)[i] = static_cast<uint8_t>(v); break;  // U8
-      }
-      break;
+    default: store_word(out, i, dt, v); break;  // MIN, MAX: the word back to the column's type
   }
 }
 
 // ------------------------------------------------------------------ host API
 namespace {
-
-bool window_dtype(DType d) {
-  return d == DType::F32 || d == DType::F64 || d == DType::I64 || d == DType::I32 || d == DType::I16 ||
-         d == DType::I8 || d == DType::U8;
-}
 
 bool value_kind(int kind) { return kind >= static_cast<int>(WindowChan::SUM_I64); }
 
@@ -489,11 +458,7 @@ void window_scan(const int64_t* words, int W, int P, int64_t n, bool reverse, co
   for (int c = 0; c < ch.n; ++c) {
     TFA_CHECK(ch.kind[c] >= 0 && ch.kind[c] <= static_cast<int>(WindowChan::MAX_WORD), "window_scan: channel ", c,
               " is of an unknown kind");
-    if (!value_kind(ch.kind[c])) continue;
-    TFA_CHECK(window_dtype(ch.dtype[c]), "window_scan: channel ", c, " has a dtype that is not supported");
-    TFA_CHECK(n == 0 || ch.ptr[c] != nullptr, "window_scan: channel ", c, " has no data");
-    TFA_CHECK(reinterpret_cast<uintptr_t>(ch.ptr[c]) % static_cast<uintptr_t>(dtype_size(ch.dtype[c])) == 0,
-              "window_scan: channel ", c, " is not aligned to its element size");
+    if (value_kind(ch.kind[c])) check_stat_column("window_scan", "channel", c, ch.dtype[c], ch.ptr[c], n);
   }
   if (n == 0) return;
   const int64_t nt = tiles_of(n);
@@ -535,7 +500,7 @@ void window_finish(const int64_t* fwd, const int64_t* rev, int64_t n, const Wind
               "window_finish: output ", o, " asks for an unknown frame");
     TFA_CHECK(sp.chan[o] >= 0 && sp.chan[o] < sp.n_chan, "window_finish: output ", o, " names channel ", sp.chan[o],
               " of ", sp.n_chan);
-    TFA_CHECK(window_dtype(sp.dtype[o]), "window_finish: output ", o, " has a dtype that is not supported");
+    TFA_CHECK(is_stat_dtype(sp.dtype[o]), "window_finish: output ", o, " has a dtype that is not supported");
     TFA_CHECK(n == 0 || sp.out[o] != nullptr, "window_finish: output ", o, " has no buffer");
   }
   if (n == 0) return;

@@ -31,9 +31,10 @@ import torch
 from ..functions import FUNCTIONS, AggregateExpression
 from ..parallel import dist
 from ..utils import dtypes as D
+from ._scalar_columns import (_aggregate_dtype, _block_on_device, _decode_sort_word, _ineligible, _scalar_column,
+                              _stat_columns, _tf_dtype)
 from .block import Block
 from .column_info import ColumnInformation
-from .stats import _decode_sort_word, _ineligible, _scalar_column, _stat_columns
 from .types import BinaryType, StringType, StructType
 
 _FIELDS = 6  # kernels.h kGroupRecordFields
@@ -48,10 +49,6 @@ class _Spec:
 
     def __init__(self, fn: str, column: Optional[str], name: str):
         self.fn, self.column, self.name = fn, column, name
-
-
-def _tf_dtype(df, name: str) -> int:
-    return ColumnInformation(df.schema[name]).stf.tf_dtype
 
 
 def _specs(df, keys: Sequence[str], exprs: Sequence[Any], what: str) -> List[_Spec]:
@@ -108,15 +105,6 @@ def _check_keys(df, keys: Sequence[str], what: str) -> None:
             raise core.InvalidTypeException(
                 f"{what}: the key '{k}' ({f.dataType}) is not a numeric scalar column of int32, int64, float32 or "
                 f"float64")
-
-
-def _out_dtype(df, s: _Spec) -> torch.dtype:
-    if s.fn == "count":
-        return torch.int64
-    vt = D.torch_dtype(_tf_dtype(df, s.column))
-    if s.fn == "sum":
-        return torch.float64 if vt.is_floating_point else torch.int64
-    return vt if s.fn in ("min", "max") else torch.float64
 
 
 # ------------------------------------------------------------------ host records
@@ -275,10 +263,6 @@ def _needed(keys, vcols):
     return list(keys) + [v for v in vcols if v not in keys]
 
 
-def _block_on_device(b: Block, names: Sequence[str]) -> bool:
-    return all(isinstance(b.columns[n], torch.Tensor) and b.columns[n].is_cuda for n in names)
-
-
 # ------------------------------------------------------------------ keyed
 def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
     """`GroupedData.agg`: see there."""
@@ -302,7 +286,7 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
     vdt = [D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]
     is_float = [t.is_floating_point for t in vdt]
     kdt = [D.torch_dtype(_tf_dtype(df, k)) for k in keys]
-    out_dt = [_out_dtype(df, s) for s in specs]
+    out_dt = [_aggregate_dtype(df, s.fn, s.column) for s in specs]
     scol = [vcols.index(s.column) if s.column is not None else 0 for s in specs]
     needed = _needed(keys, vcols)
     keep_on_device = any(b.columns[n].is_cuda for b in (df._cached or {}).values() if b.nrows for n in needed

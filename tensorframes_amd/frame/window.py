@@ -44,10 +44,10 @@ import torch
 
 from ..parallel import dist
 from ..utils import dtypes as D
+from ._scalar_columns import (_aggregate_dtype, _block_on_device, _decode_sort_word, _ineligible, _scalar_column,
+                              _tf_dtype)
 from .block import Block
 from .column import Column, _describe
-from .column_info import ColumnInformation
-from .stats import _decode_sort_word, _ineligible, _scalar_column
 
 _MAX_CHANNELS = 16  # kernels.h kMaxPackCols: channels per scan, outputs per _C.window_finish call
 _RANKING = ("row_number", "rank", "dense_rank")
@@ -460,25 +460,9 @@ class _Plan:
         return len(self.kinds) - 1
 
 
-def _tf_dtype(df, name: str) -> int:
-    return ColumnInformation(df.schema[name]).stf.tf_dtype
-
-
 def _out_dtype(df, e: WindowExpression) -> torch.dtype:
-    if e.fn in _RANKING:
-        return torch.int32
-    if e.fn == "count":
-        return torch.int64
-    vt = D.torch_dtype(_tf_dtype(df, e.column))
-    if e.fn == "sum":
-        return torch.float64 if vt.is_floating_point else torch.int64
-    return vt if e.fn in ("min", "max") else torch.float64
-
-
-def _block_on_device(b: Block, names: Sequence[str]) -> bool:
-    cols = [b.columns[n] for n in names]
-    return bool(cols) and all(isinstance(c, torch.Tensor) and c.is_cuda for c in cols) and \
-        len({c.device for c in cols}) == 1
+    # (the ranking functions exist over a window only; the aggregates follow groupBy().agg)
+    return torch.int32 if e.fn in _RANKING else _aggregate_dtype(df, e.fn, e.column)
 
 
 def _device_cached(df) -> bool:

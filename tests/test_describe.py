@@ -286,7 +286,7 @@ def test_mean_and_stddev_against_exact_arithmetic(dtype, n):
 # ------------------------------------------------------------------ exact values
 @pytest.mark.parametrize("dtype", WORD_DTYPES)
 def test_decode_sort_word_inverts_the_table(dtype):
-    from tensorframes_amd.frame.stats import _decode_sort_word
+    from tensorframes_amd.frame._scalar_columns import _decode_sort_word
     dt = np.dtype(dtype)
     if dt.kind == "f":
         fi = np.finfo(dt)
