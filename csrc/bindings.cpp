@@ -1167,6 +1167,172 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "values have dtype dtypes[o]. count and integer sums are int64, min / max the column's dtype (words decoded: "
      "-0.0 comes back as 0.0), the others float64; a NaN or opposite infinities in a float group give NaN, the "
      "sample statistics NaN below two rows");
+  // corr / covar_samp / covar_pop on device-resident columns (kernels/stats.hip, kernels/group_stats.hip)
+  // xs[q], ys[q]: 1..kMaxPackCols pairs, all columns on one device and of one length
+  auto pair_cols_from = [](const char* what, const std::vector<at::Tensor>& xs, const std::vector<at::Tensor>& ys,
+                           k::StatCols* sx, k::StatCols* sy) {
+    if (xs.size() != ys.size())
+      throw py::value_error(str_cat(what, ": ", xs.size(), " first columns, ", ys.size(), " second columns"));
+    if (xs.empty() || xs.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat(what, ": 1..", k::kMaxPackCols, " pairs per call, got ", xs.size()));
+    *sx = stat_cols_from(what, xs);
+    *sy = stat_cols_from(what, ys);
+    if (ys[0].device() != xs[0].device())
+      throw py::value_error(str_cat(what, ": the second columns are not on the first columns' device"));
+    if (ys[0].size(0) != xs[0].size(0))
+      throw py::value_error(str_cat(what, ": the second columns have ", ys[0].size(0), " rows, the first columns ",
+                                    xs[0].size(0)));
+  };
+  // int64 device pair records [*, Q, 7], contiguous
+  auto pair_records = [](const char* what, const at::Tensor& t) {
+    if (!t.is_cuda()) throw py::value_error(str_cat(what, ": the records must be a device tensor"));
+    if (t.scalar_type() != at::kLong) throw py::type_error(str_cat(what, ": the records must be int64 bit patterns"));
+    if (t.dim() != 3 || t.size(2) != k::kPairRecordFields || t.size(1) < 1 || t.size(1) > k::kMaxPackCols)
+      throw py::value_error(str_cat(what, ": records [*, 1..", k::kMaxPackCols, ", ", k::kPairRecordFields,
+                                    "] expected"));
+    if (!t.is_contiguous()) throw py::value_error(str_cat(what, ": the records are not contiguous"));
+  };
+  m.def("column_pair_moments", [pair_cols_from](const std::vector<at::Tensor>& xs, const std::vector<at::Tensor>& ys) {
+    k::StatCols sx, sy;
+    pair_cols_from("column_pair_moments", xs, ys, &sx, &sy);
+    const int64_t n = xs[0].size(0), Q = sx.n;
+    const auto dev = xs[0].device();
+    if (n == 0) return at::zeros({Q, k::kPairRecordFields}, at::kLong).to(dev);  // nothing is launched
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    at::Tensor rec = pool_empty({Q, k::kPairRecordFields}, xs[0].options().dtype(at::kLong));
+    const size_t wsb = k::column_pair_moments_workspace_bytes(sx.n, n);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, xs[0].options().dtype(at::kLong));
+    k::column_pair_moments(sx, sy, n, rec.data_ptr<int64_t>(), ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    return rec;
+  }, py::arg("xs"), py::arg("ys"),
+     "up to 16 pairs (xs[q], ys[q]) of dense scalar device columns [n] (mixed dtypes, contiguous; a column may appear "
+     "in several pairs) -> int64 records [Q, 7] (bit patterns): n, mean_x, mean_y, M2_x, M2_y, C_xy = sum (x - mean_x)"
+     "(y - mean_y) as f64 and the count of rows whose x or y is NaN or an infinity; the same bits on every run. "
+     "n == 0 launches nothing and gives empty records (all zeros)");
+  m.def("group_pair_moments", [pair_cols_from, group_index](const std::vector<at::Tensor>& xs,
+                                                            const std::vector<at::Tensor>& ys, const at::Tensor& perm,
+                                                            const at::Tensor& offsets) {
+    k::StatCols sx, sy;
+    pair_cols_from("group_pair_moments", xs, ys, &sx, &sy);
+    const auto dev = xs[0].device();
+    group_index("group_pair_moments", "perm", perm, dev);
+    group_index("group_pair_moments", "offsets", offsets, dev);
+    const int64_t n = xs[0].size(0), Q = sx.n;
+    if (perm.size(0) != n)
+      throw py::value_error(str_cat("group_pair_moments: perm has ", perm.size(0), " entries, the columns ", n,
+                                    " rows"));
+    if (offsets.size(0) < 1) throw py::value_error("group_pair_moments: offsets [nseg + 1] expected, got none");
+    const int64_t nseg = offsets.size(0) - 1;
+    if (n == 0 || nseg == 0) return at::zeros({nseg, Q, k::kPairRecordFields}, at::kLong).to(dev);
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    at::Tensor rec = pool_empty({nseg, Q, k::kPairRecordFields}, xs[0].options().dtype(at::kLong));
+    const size_t wsb = k::group_pair_moments_workspace_bytes(sx.n, n, nseg);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, xs[0].options().dtype(at::kLong));
+    {
+      py::gil_scoped_release nogil;
+      k::group_pair_moments(sx, sy, n, perm.data_ptr<int64_t>(), n, offsets.data_ptr<int64_t>(), nseg,
+                            rec.data_ptr<int64_t>(), ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    }
+    return rec;
+  }, py::arg("xs"), py::arg("ys"), py::arg("perm"), py::arg("offsets"),
+     "up to 16 pairs (xs[q], ys[q]) of dense scalar device columns [n] and segment_csr's (perm [n], offsets "
+     "[nseg + 1]) -> int64 pair records [nseg, Q, 7] (column_pair_moments' fields). group_moments' work items; a "
+     "record depends on its segment's rows in row order alone. n == 0 launches nothing and gives empty records");
+  m.def("group_both_moments", [pair_cols_from, group_index](const std::vector<at::Tensor>& cols,
+                                                            const std::vector<at::Tensor>& xs,
+                                                            const std::vector<at::Tensor>& ys, const at::Tensor& perm,
+                                                            const at::Tensor& offsets) {
+    const k::StatCols sc = stat_cols_from("group_both_moments", cols);
+    k::StatCols sx, sy;
+    pair_cols_from("group_both_moments", xs, ys, &sx, &sy);
+    const auto dev = cols[0].device();
+    const int64_t n = cols[0].size(0), C = sc.n, Q = sx.n;
+    if (xs[0].device() != dev || xs[0].size(0) != n)
+      throw py::value_error("group_both_moments: the pair columns are not on the columns' device or of their length");
+    group_index("group_both_moments", "perm", perm, dev);
+    group_index("group_both_moments", "offsets", offsets, dev);
+    if (perm.size(0) != n)
+      throw py::value_error(str_cat("group_both_moments: perm has ", perm.size(0), " entries, the columns ", n,
+                                    " rows"));
+    if (offsets.size(0) < 1) throw py::value_error("group_both_moments: offsets [nseg + 1] expected, got none");
+    const int64_t nseg = offsets.size(0) - 1;
+    if (n == 0 || nseg == 0) {
+      at::Tensor rec = at::zeros({nseg, C, k::kGroupRecordFields}, at::kLong);
+      if (nseg) rec.select(2, 4).fill_(-1);  // (all ones)
+      return py::make_tuple(rec.to(dev), at::zeros({nseg, Q, k::kPairRecordFields}, at::kLong).to(dev));
+    }
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    const auto opts = cols[0].options().dtype(at::kLong);
+    at::Tensor rec = pool_empty({nseg, C, k::kGroupRecordFields}, opts);
+    at::Tensor prec = pool_empty({nseg, Q, k::kPairRecordFields}, opts);
+    const size_t ib = k::group_items_workspace_bytes(nseg);
+    const size_t wa = k::group_moments_workspace_bytes(sc.n, n, nseg);
+    const size_t wb = k::group_pair_moments_workspace_bytes(sx.n, n, nseg);
+    at::Tensor wi = pool_empty({static_cast<int64_t>((ib + 7) / 8)}, opts);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((std::max(wa, wb) + 7) / 8)}, opts);
+    {
+      py::gil_scoped_release nogil;
+      // the work items are built once; both passes run in stream order and share the workspace of partial records
+      const k::GroupItems items = k::group_items(offsets.data_ptr<int64_t>(), nseg, n, wi.data_ptr(),
+                                                 static_cast<size_t>(wi.numel()) * 8, s);
+      k::group_moments(sc, n, perm.data_ptr<int64_t>(), n, offsets.data_ptr<int64_t>(), nseg, rec.data_ptr<int64_t>(),
+                       ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s, &items);
+      k::group_pair_moments(sx, sy, n, perm.data_ptr<int64_t>(), n, offsets.data_ptr<int64_t>(), nseg,
+                            prec.data_ptr<int64_t>(), ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s, &items);
+    }
+    return py::make_tuple(rec, prec);
+  }, py::arg("cols"), py::arg("xs"), py::arg("ys"), py::arg("perm"), py::arg("offsets"),
+     "group_moments(cols, perm, offsets) and group_pair_moments(xs, ys, perm, offsets) of one CSR -> (records "
+     "[nseg, C, 6], pair records [nseg, Q, 7]), the same bits as the two calls; the work items (chunk counts and "
+     "their scan, one stream synchronisation) are built once for both");
+  m.def("merge_pair_records", [pair_records, group_index](const at::Tensor& recs, const at::Tensor& offsets) {
+    pair_records("merge_pair_records", recs);
+    group_index("merge_pair_records", "offsets", offsets, recs.device());
+    const int64_t mm = recs.size(0), Q = recs.size(1);
+    if (offsets.size(0) < 1) throw py::value_error("merge_pair_records: offsets [ng + 1] expected, got none");
+    const int64_t ng = offsets.size(0) - 1;
+    c10::hip::HIPGuard guard(recs.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(recs.device().index()).stream();
+    at::Tensor out = pool_empty({ng, Q, k::kPairRecordFields}, recs.options());
+    k::merge_pair_records(mm ? recs.data_ptr<int64_t>() : nullptr, mm, static_cast<int>(Q),
+                          offsets.data_ptr<int64_t>(), ng, out.data_ptr<int64_t>(), s);
+    return out;
+  }, py::arg("records"), py::arg("offsets"),
+     "pair records [m, Q, 7] ordered by (key, partition) and CSR offsets [ng + 1] over them -> [ng, Q, 7]: each "
+     "group's records merged in order with Chan's formula (the non-finite counts add)");
+  m.def("pair_results", [pair_records](const at::Tensor& recs, const std::vector<int64_t>& pairs,
+                                       const std::vector<std::string>& stats) {
+    static const char* const names[] = {"corr", "covar_samp", "covar_pop"};
+    pair_records("pair_results", recs);
+    const int64_t ng = recs.size(0), Q = recs.size(1);
+    if (pairs.empty() || pairs.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("pair_results: 1..", k::kMaxPackCols, " outputs per call, got ", pairs.size()));
+    if (stats.size() != pairs.size()) throw py::value_error("pair_results: one statistic per output expected");
+    k::PairResultSpec spec;
+    spec.n = static_cast<int>(pairs.size());
+    c10::hip::HIPGuard guard(recs.device().index());
+    std::vector<at::Tensor> outs;
+    for (size_t o = 0; o < pairs.size(); ++o) {
+      if (pairs[o] < 0 || pairs[o] >= Q)
+        throw py::value_error(str_cat("pair_results: output ", o, " names pair ", pairs[o], " of ", Q));
+      const int st = name_index(names, stats[o]);
+      if (st < 0) throw py::value_error(str_cat("pair_results: '", stats[o], "' is not a pair statistic"));
+      outs.push_back(pool_empty({ng}, recs.options().dtype(at::kDouble)));
+      spec.pair[o] = static_cast<int>(pairs[o]);
+      spec.stat[o] = static_cast<k::PairStat>(st);
+      spec.out[o] = outs.back().data_ptr<double>();
+    }
+    k::pair_results(ng ? recs.data_ptr<int64_t>() : nullptr, ng, static_cast<int>(Q), spec,
+                    c10::hip::getCurrentHIPStream(recs.device().index()).stream());
+    return outs;
+  }, py::arg("records"), py::arg("pairs"), py::arg("stats"),
+     "merged pair records [ng, Q, 7] -> one float64 device column [ng] per output (up to 16, one launch): output o is "
+     "stats[o] (corr, covar_samp, covar_pop) of pair pairs[o]. covar_pop = C / n (NaN without rows), covar_samp = "
+     "C / (n - 1) (NaN below two rows), corr = C / sqrt(M2_x * M2_y) (NaN without rows or where an M2 is 0, not "
+     "clamped); NaN where the record counts a row with a NaN or an infinity");
   // Window / .over() on device-resident partitions (kernels/window_scan.hip)
   m.def("window_tile_rows", [] { return k::window_tile_rows(); }, "rows per tile of window_scan");
   // int64 device bit patterns [rows, n], contiguous

@@ -249,6 +249,21 @@ struct StatCols {
 size_t column_moments_workspace_bytes(int ncols, int64_t n);
 void column_moments(const StatCols& cols, int64_t n, double* moments, int64_t* extremes, void* workspace,
                     size_t workspace_size, hipStream_t s);
+// one pair record per (xs[q], ys[q]) in one launch pair, for corr / covar_samp
+// / covar_pop: records[q] = kPairRecordFields int64 bit patterns {n, mean_x,
+// mean_y, M2_x, M2_y, C_xy = sum (x - mean_x)(y - mean_y)} as f64 (every
+// element converted to f64 first) and the count of rows whose x or y is NaN or
+// an infinity. The two columns of a pair may differ in dtype and alignment; a
+// column may appear in several pairs. A lane takes runs of 16 consecutive rows
+// (16-byte vector loads where a column's runs are aligned, scalar loads
+// otherwise), the runs enter as batches, lanes, waves and blocks are merged in
+// order with Chan's formula: no float atomics, the same bits on every run, a
+// function of the row count alone. n == 0 launches nothing and leaves records
+// alone (the caller fills zeros: the empty record).
+constexpr int kPairRecordFields = 7;
+size_t column_pair_moments_workspace_bytes(int npairs, int64_t n);
+void column_pair_moments(const StatCols& xs, const StatCols& ys, int64_t n, int64_t* records, void* workspace,
+                         size_t workspace_size, hipStream_t s);
 // hist[p][d] (device int64 [P][256], overwritten) = rows whose word has its top
 // prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] (host) and whose
 // next 8-bit digit is d; prefix_bits == 0 takes P == 1 and ignores the prefix.
@@ -274,9 +289,30 @@ int group_chunk_rows();  // rows per work item of group_moments
 // in chunk order. The chunk counts are scanned on the device and the stream
 // is synchronised once to read their total. A record depends on the
 // segment's rows in row order alone. n == 0 or nseg == 0 launches nothing.
+// The work items are built by group_items (the chunk count and its scan, one
+// stream synchronisation); a caller that needs both record kinds of one CSR
+// builds them once and hands them to both passes (`items`), otherwise each
+// pass builds its own in its workspace.
+struct GroupItems {
+  const int64_t* coffs = nullptr;  // device [nseg + 1]: the exclusive scan of the segments' chunk counts
+  int64_t items = 0;               // coffs[nseg]
+};
+size_t group_items_workspace_bytes(int64_t nseg);
+GroupItems group_items(const int64_t* offsets, int64_t nseg, int64_t nperm, void* workspace, size_t workspace_size,
+                       hipStream_t s);
 size_t group_moments_workspace_bytes(int ncols, int64_t nperm, int64_t nseg);
 void group_moments(const StatCols& cols, int64_t n, const int64_t* perm, int64_t nperm, const int64_t* offsets,
-                   int64_t nseg, int64_t* records, void* workspace, size_t workspace_size, hipStream_t s);
+                   int64_t nseg, int64_t* records, void* workspace, size_t workspace_size, hipStream_t s,
+                   const GroupItems* items = nullptr);
+// pair records [nseg][xs.n][kPairRecordFields] (the stats section) of the same
+// CSR segments and work items: Welford per lane over rows gathered through
+// perm, the lanes merged in lane order, a segment's chunks folded in chunk
+// order. A record depends on the segment's rows in row order alone. n == 0
+// or nseg == 0 launches nothing.
+size_t group_pair_moments_workspace_bytes(int npairs, int64_t nperm, int64_t nseg);
+void group_pair_moments(const StatCols& xs, const StatCols& ys, int64_t n, const int64_t* perm, int64_t nperm,
+                        const int64_t* offsets, int64_t nseg, int64_t* records, void* workspace, size_t workspace_size,
+                        hipStream_t s, const GroupItems* items = nullptr);
 // out [ng][ncols][6] = records [m][ncols][6] rows offsets[g] .. offsets[g + 1]
 // merged in order (Chan; integer sums add, float sums add in that order, words
 // take min / max), starting from the group's first record. Bit c of
@@ -295,6 +331,23 @@ struct GroupResultSpec {
 // decoded to the column's type, describe's NaN / infinity rule (decided from
 // the extreme words), the sample statistics NaN below two rows
 void group_results(const int64_t* records, int64_t ng, int ncols, const GroupResultSpec& spec, hipStream_t s);
+// out [ng][npairs][7] = pair records [m][npairs][7] rows offsets[g] ..
+// offsets[g + 1] merged in order (Chan; the non-finite counts add), starting
+// from the group's first record; a group without records gets the empty one
+void merge_pair_records(const int64_t* records, int64_t m, int npairs, const int64_t* offsets, int64_t ng,
+                        int64_t* out, hipStream_t s);
+enum class PairStat : int { CORR = 0, COVAR_SAMP, COVAR_POP };
+struct PairResultSpec {
+  int n = 0;
+  int pair[kMaxPackCols];  // the record pair an output reads
+  PairStat stat[kMaxPackCols];
+  double* out[kMaxPackCols];  // [ng]
+};
+// every output column of merged pair records [ng][npairs][7] in one launch:
+// covar_pop = C / n (NaN without rows), covar_samp = C / (n - 1) (NaN below two
+// rows), corr = C / sqrt(M2_x * M2_y) (NaN without rows or where an M2 is 0;
+// not clamped); all three NaN where the record counts a non-finite row
+void pair_results(const int64_t* records, int64_t ng, int npairs, const PairResultSpec& spec, hipStream_t s);
 
 // ------------------------------------------------------------ window functions (window_scan.hip)
 // Window / .over(). The n rows of one partition are sorted by (partition

@@ -11,6 +11,14 @@
 //            the column's alignment alone, never on the run. Up to
 //            kMaxPackCols columns of mixed dtypes in one launch pair (the
 //            column is the grid's y).
+//   pairs    per pair of columns one record {n, mean_x, mean_y, M2_x, M2_y,
+//            C_xy, rows with a NaN or an infinity} (moments.h PairRec) for
+//            corr / covar_samp / covar_pop: the structure of moments, the
+//            pair on the grid's y. A lane takes runs of 16 consecutive rows of
+//            both columns (whole 16-byte vectors of every dtype; a column
+//            whose runs are not 16-byte aligned is read with scalar loads), a
+//            run entering as one batch. The result depends on the row count
+//            alone. Nothing is ever computed as sum(xy) - n mean_x mean_y.
 //   hist     one step of a most-significant-digit-first radix select: for up
 //            to kMaxPackCols word prefixes, the 256-bin histogram of the next
 //            8-bit digit over the rows whose word starts with the prefix. The
@@ -219,6 +227,153 @@ __global__ __launch_bounds__(kT) void moments_final_kernel(const Rec* __restrict
   }
 }
 
+// ------------------------------------------------------------------ pairs
+namespace {
+
+// The two columns of a pair differ in element width and alignment: a lane
+// takes runs of kRun consecutive rows of both, whole 16-byte vectors of every
+// dtype (1 for the one-byte types, 8 for the eight-byte ones).
+constexpr int kRun = 16;
+
+// rows [lo, ..) of the column start on a 16-byte boundary (lo: uniform)
+template <typename T>
+__device__ __forceinline__ bool run_aligned(const void* __restrict__ src, int64_t lo) {
+  return (reinterpret_cast<uintptr_t>(static_cast<const T*>(src) + lo) & 15u) == 0;
+}
+
+// rows [r0, r0 + kRun) as f64: every load is issued before the first use
+// (kRun * sizeof(T) / 16 vector loads where `vec`, kRun scalar ones otherwise)
+template <typename T>
+__device__ __forceinline__ void load_run(const void* __restrict__ src, int64_t r0, bool vec, double (&v)[kRun]) {
+  constexpr int V = Vec16<T>::V;
+  using VT = typename Vec16<T>::type;
+  const T* __restrict__ p = static_cast<const T*>(src) + r0;
+  if (vec) {
+    const VT* __restrict__ pv = reinterpret_cast<const VT*>(p);
+    VT t[kRun / V];
+#pragma unroll
+    for (int j = 0; j < kRun / V; ++j) t[j] = pv[j];
+#pragma unroll
+    for (int j = 0; j < kRun / V; ++j) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) v[j * V + i] = static_cast<double>(static_cast<T>(t[j][i]));
+    }
+  } else {
+    T t[kRun];
+#pragma unroll
+    for (int j = 0; j < kRun; ++j) t[j] = p[j];
+#pragma unroll
+    for (int j = 0; j < kRun; ++j) v[j] = static_cast<double>(t[j]);
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ double load_row(const void* __restrict__ src, int64_t r) {
+  return static_cast<double>(static_cast<const T*>(src)[r]);
+}
+
+// The kRun rows of one run enter together, as the V rows of one load do in
+// lane_moments: the run's means, squared deviations and co-deviations, then
+// one merge in Chan's form (one division per run, not three per row).
+__device__ __forceinline__ void pair_add_run(PairRec& r, const double (&x)[kRun], const double (&y)[kRun]) {
+  double sx[4] = {0.0, 0.0, 0.0, 0.0}, sy[4] = {0.0, 0.0, 0.0, 0.0};
+  uint64_t bad = 0;
+#pragma unroll
+  for (int j = 0; j < kRun; ++j) {
+    sx[j & 3] += x[j];
+    sy[j & 3] += y[j];
+    bad += (__builtin_isfinite(x[j]) && __builtin_isfinite(y[j])) ? 0ull : 1ull;
+  }
+  const double bmx = ((sx[0] + sx[1]) + (sx[2] + sx[3])) * (1.0 / kRun);  // (kRun is a power of two)
+  const double bmy = ((sy[0] + sy[1]) + (sy[2] + sy[3])) * (1.0 / kRun);
+  double b2x[2] = {0.0, 0.0}, b2y[2] = {0.0, 0.0}, bc[2] = {0.0, 0.0};
+#pragma unroll
+  for (int j = 0; j < kRun; ++j) {
+    const double dx = x[j] - bmx, dy = y[j] - bmy;
+    b2x[j & 1] = fma(dx, dx, b2x[j & 1]);
+    b2y[j & 1] = fma(dy, dy, b2y[j & 1]);
+    bc[j & 1] = fma(dx, dy, bc[j & 1]);
+  }
+  const double tot = r.n + kRun;
+  const double f = kRun / tot;
+  const double dx = bmx - r.mx, dy = bmy - r.my;
+  const double w = r.n * f;  // (n == 0: nothing of the deltas, however large)
+  r.mx += dx * f;
+  r.my += dy * f;
+  r.m2x += (b2x[0] + b2x[1]) + (w * dx) * dx;
+  r.m2y += (b2y[0] + b2y[1]) + (w * dy) * dy;
+  r.cxy += (bc[0] + bc[1]) + (w * dx) * dy;
+  r.n = tot;
+  r.bad += bad;
+}
+
+// the block's pair record in thread 0: lanes in lane order, then the waves in
+// wave order
+__device__ __forceinline__ PairRec block_merge_pairs(PairRec r, PairRec* lds /*[kWaves]*/) {
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  r = wave_merge_pairs(r);
+  if (lane == 0) lds[w] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < kWaves; ++i) r = merge_pairs(r, lds[i]);
+  }
+  return r;
+}
+
+}  // namespace
+
+// block (b, q): rows [b * chunk, min(n, (b + 1) * chunk)) of pair q -> part[q][b].
+// chunk is a multiple of kRun. Thread t takes the runs t, t + kT, ...; the
+// rows after the last whole run (fewer than kRun, in the last block alone) go
+// one to a thread, through Welford's update. Whether a column's runs are read
+// as vectors is decided per block from the address of its first row.
+__global__ __launch_bounds__(kT) void pair_moments_partial_kernel(StatCols xs, StatCols ys, int64_t n, int64_t chunk,
+                                                                  PairRec* __restrict__ part) {
+  __shared__ PairRec lds[kWaves];
+  const int q = blockIdx.y;
+  const int64_t first = (int64_t)blockIdx.x * chunk;
+  const int64_t lo = first < n ? first : n;
+  const int64_t hi = lo + chunk < n ? lo + chunk : n;
+  const void* px = xs.ptr[q];
+  const void* py = ys.ptr[q];
+  const DType tx = xs.dtype[q], ty = ys.dtype[q];
+  // (dtypes and alignments are uniform: scalar branches)
+  const bool vx = dispatch_column(tx, [&](auto tag) { return run_aligned<decltype(tag)>(px, lo); });
+  const bool vy = dispatch_column(ty, [&](auto tag) { return run_aligned<decltype(tag)>(py, lo); });
+  const int64_t nrun = (hi - lo) / kRun;
+  PairRec r = pair_empty();
+  for (int64_t j = threadIdx.x; j < nrun; j += kT) {
+    const int64_t r0 = lo + j * kRun;
+    double x[kRun], y[kRun];
+    dispatch_column(tx, [&](auto tag) { load_run<decltype(tag)>(px, r0, vx, x); });
+    dispatch_column(ty, [&](auto tag) { load_run<decltype(tag)>(py, r0, vy, y); });
+    pair_add_run(r, x, y);
+  }
+  const int64_t t0 = lo + nrun * kRun + threadIdx.x;
+  if (t0 < hi) {
+    const double x = dispatch_column(tx, [&](auto tag) { return load_row<decltype(tag)>(px, t0); });
+    const double y = dispatch_column(ty, [&](auto tag) { return load_row<decltype(tag)>(py, t0); });
+    pair_add_row(r, x, y);
+  }
+  r = block_merge_pairs(r, lds);
+  if (threadIdx.x == 0) part[(int64_t)q * gridDim.x + blockIdx.x] = r;
+}
+
+// block q: part[q][0 .. nb) merged in block order -> records[q]
+__global__ __launch_bounds__(kT) void pair_moments_final_kernel(const PairRec* __restrict__ part, int nb,
+                                                                int64_t* __restrict__ records) {
+  __shared__ PairRec lds[kWaves];
+  const int q = blockIdx.x;
+  const PairRec* __restrict__ p = part + (int64_t)q * nb;
+  const int per = (nb + kT - 1) / kT;  // consecutive records per thread
+  const int a = threadIdx.x * per, b = a + per < nb ? a + per : nb;
+  PairRec r = pair_empty();
+  for (int i = a; i < b; ++i) r = merge_pairs(r, p[i]);
+  r = block_merge_pairs(r, lds);
+  if (threadIdx.x == 0) store_pair(records + (int64_t)q * kPairRecordFields, r);
+}
+
 namespace {
 
 struct HistPrefixes {
@@ -315,6 +470,37 @@ void column_moments(const StatCols& cols, int64_t n, double* moments, int64_t* e
   TFA_LAUNCH_CHECK("moments_partial_kernel");
   hipLaunchKernelGGL(moments_final_kernel, dim3(cols.n), dim3(kT), 0, s, (const Rec*)part, nb, moments, extremes);
   TFA_LAUNCH_CHECK("moments_final_kernel");
+}
+
+size_t column_pair_moments_workspace_bytes(int npairs, int64_t n) {
+  if (n <= 0 || npairs <= 0) return 0;
+  int nb;
+  int64_t chunk;
+  moments_grid(n, &nb, &chunk);
+  return radix::align_up(static_cast<size_t>(npairs) * nb * sizeof(PairRec));
+}
+
+void column_pair_moments(const StatCols& xs, const StatCols& ys, int64_t n, int64_t* records, void* ws, size_t ws_size,
+                         hipStream_t s) {
+  TFA_CHECK(xs.n >= 1 && xs.n <= kMaxPackCols, "column_pair_moments: 1..", kMaxPackCols, " pairs, got ", xs.n);
+  TFA_CHECK(xs.n == ys.n, "column_pair_moments: ", xs.n, " first columns, ", ys.n, " second columns");
+  TFA_CHECK(n >= 0, "column_pair_moments: negative row count");
+  check_stat_columns("column_pair_moments", xs, n);
+  check_stat_columns("column_pair_moments", ys, n);
+  if (n == 0) return;
+  TFA_CHECK(records != nullptr && ws != nullptr, "column_pair_moments: null buffer");
+  TFA_CHECK(reinterpret_cast<uintptr_t>(records) % 8 == 0 && reinterpret_cast<uintptr_t>(ws) % 8 == 0,
+            "column_pair_moments: unaligned buffer");
+  TFA_CHECK(ws_size >= column_pair_moments_workspace_bytes(xs.n, n), "column_pair_moments: workspace too small");
+  int nb;
+  int64_t chunk;
+  moments_grid(n, &nb, &chunk);  // (chunk: a multiple of 16 == kRun)
+  static_assert(kRun == 16, "moments_grid rounds a block's rows to 16");
+  PairRec* part = static_cast<PairRec*>(ws);
+  hipLaunchKernelGGL(pair_moments_partial_kernel, dim3(nb, xs.n), dim3(kT), 0, s, xs, ys, n, chunk, part);
+  TFA_LAUNCH_CHECK("pair_moments_partial_kernel");
+  hipLaunchKernelGGL(pair_moments_final_kernel, dim3(xs.n), dim3(kT), 0, s, (const PairRec*)part, nb, records);
+  TFA_LAUNCH_CHECK("pair_moments_final_kernel");
 }
 
 void select_hist(DType dtype, const void* col, int64_t n, const int64_t* prefixes, int P, int prefix_bits,

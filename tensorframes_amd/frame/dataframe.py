@@ -647,9 +647,24 @@ class DataFrame:
         from .group_agg import group_agg
         return group_agg(GroupedData(self, []), list(exprs))
 
+    def corr(self, col1, col2, method="pearson") -> float:
+        """Pearson's correlation coefficient of two numeric scalar columns as a
+        Python float (`df.stat.corr`): `agg(F.corr(col1, col2))`, NaN where
+        Spark gives null (no rows, a constant column, a NaN or an infinity in
+        either column). Any `method` but "pearson" raises ValueError. An
+        action, and collective."""
+        return self.stat.corr(col1, col2, method)
+
+    def cov(self, col1, col2) -> float:
+        """The sample covariance of two numeric scalar columns as a Python
+        float (`df.stat.cov`): `agg(F.covar_samp(col1, col2))`, NaN below two
+        rows. An action, and collective."""
+        return self.stat.cov(col1, col2)
+
     @property
     def stat(self):
-        """Spark's `df.stat` accessor (`df.stat.approxQuantile(...)`)."""
+        """Spark's `df.stat` accessor (`df.stat.approxQuantile(...)`,
+        `df.stat.corr(...)`, `df.stat.cov(...)`)."""
         from .stats import DataFrameStatFunctions
         return DataFrameStatFunctions(self)
 
@@ -1165,9 +1180,12 @@ class GroupedData:
         keys in ascending order. Values follow `describe`: sample statistics
         are NaN for a one-row group, a NaN in a group makes its sum, avg,
         stddev and variance NaN, min / max order NaN last and return -0.0 as
-        0.0. Device-resident partitions are reduced by the grouped-moments
-        kernel (kernels/group_stats.hip); for a given partitioning the result
-        has the same bits for every number of ranks."""
+        0.0. `F.corr(a, b)`, `F.covar_samp(a, b)` and `F.covar_pop(a, b)` mix
+        in freely (float64, `corr(a, b)`; at most 16 distinct ordered pairs
+        per call): NaN where Spark gives null, and for a group with a NaN or an
+        infinity in either column. Device-resident partitions are reduced by
+        the grouped-moments kernels (kernels/group_stats.hip); for a given
+        partitioning the result has the same bits for every number of ranks."""
         from .group_agg import group_agg
         return group_agg(self, list(exprs))
 

@@ -3,13 +3,22 @@
 Per group and value column one record of six 8-byte fields travels as int64
 bit patterns: n, mean, M2 (f64; every element converted to f64 first), the sum
 (wrapping int64 for integer columns, an f64 running sum for float ones), and
-the smallest and largest ascending sort word.
+the smallest and largest ascending sort word. `corr`, `covar_samp` and
+`covar_pop` have a record of their own per (group, ordered pair of value
+columns), seven fields: n, mean_x, mean_y, M2_x, M2_y, the co-moment
+C_xy = sum (x - mean_x)(y - mean_y) (f64) and the integer count of rows whose
+x or y is NaN or an infinity; the empty record is all zeros. Pair records ride
+with the one-column records through both stages (one row per group for the
+all-to-all) and are merged by their own merge.
 
 * stage 1: every partition is reduced on its own. Keys are factorised by
   `ops/groupby.group_ids` (the grouping of `groupBy(keys).count()`); device
   partitions go through `_C.segment_csr` + `_C.group_moments`
   (kernels/group_stats.hip), host partitions through numpy (two-pass f64 per
-  group). One record per (group of the partition, column).
+  group). One record per (group of the partition, column); pair records come
+  from `_C.group_pair_moments` (the same work items, built once when a call
+  needs both kinds), or from `_C.column_pair_moments` for `DataFrame.agg`,
+  which reads a device partition densely, without a one-segment gather.
 * stage 2: the records of all partitions, tagged with their partition id,
   are routed to the rank their key hashes to (`ops/groupby.route`: one
   all-to-all, the partition id and the record fields riding as ordinary
@@ -28,7 +37,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..functions import FUNCTIONS, AggregateExpression
+from ..functions import FUNCTIONS, AggregateExpression, PairAggregateExpression
 from ..parallel import dist
 from ..utils import dtypes as D
 from ._scalar_columns import (_aggregate_dtype, _block_on_device, _decode_sort_word, _ineligible, _scalar_column,
@@ -41,14 +50,17 @@ _FIELDS = 6  # kernels.h kGroupRecordFields
 _MAX_COLS = 16  # value columns per agg call, outputs per _C.group_results call (kernels.h kMaxPackCols)
 _KEY_DTYPES = (D.DT_INT32, D.DT_INT64, D.DT_FLOAT, D.DT_DOUBLE)
 _N, _MEAN, _M2, _SUM, _LO, _HI = range(_FIELDS)
+_PFIELDS = 7  # kernels.h kPairRecordFields
+_PN, _PMX, _PMY, _PM2X, _PM2Y, _PC, _PBAD = range(_PFIELDS)
 
 
 # ------------------------------------------------------------------ expressions
 class _Spec:
-    """One output column: statistic `fn` of value column `column` (None: rows)."""
+    """One output column: statistic `fn` of value column `column` (None: rows),
+    or pair statistic `fn` of the ordered pair of value columns `pair`."""
 
-    def __init__(self, fn: str, column: Optional[str], name: str):
-        self.fn, self.column, self.name = fn, column, name
+    def __init__(self, fn: str, column: Optional[str], name: str, pair: Optional[Tuple[str, str]] = None):
+        self.fn, self.column, self.name, self.pair = fn, column, name, pair
 
 
 def _specs(df, keys: Sequence[str], exprs: Sequence[Any], what: str) -> List[_Spec]:
@@ -69,6 +81,15 @@ def _specs(df, keys: Sequence[str], exprs: Sequence[Any], what: str) -> List[_Sp
         raise ValueError(f"{what}: at least one aggregate expression is expected")
     out: List[_Spec] = []
     for e in exprs:
+        if isinstance(e, PairAggregateExpression):
+            for c in (e.x, e.y):
+                if c not in df.schema:
+                    raise ValueError(f"{what}: Column {c} not found in {df.columns}")
+                err = _ineligible(df, c, what)
+                if err is not None:
+                    raise err
+            out.append(_Spec(e.fn, None, e.output_name, (e.x, e.y)))
+            continue
         if not isinstance(e, AggregateExpression):
             hint = " (Column.sum() and friends reduce the cell of one row; use tfs.functions.sum(name))" \
                 if type(e).__name__ == "Column" else ""
@@ -228,18 +249,132 @@ def _host_results(recs: np.ndarray, cols: Sequence[int], stats: Sequence[str], d
     return outs
 
 
+# ------------------------------------------------------------------ host pair records
+def _host_pair_records(xs: Sequence[torch.Tensor], ys: Sequence[torch.Tensor], ids: np.ndarray, ng: int) -> np.ndarray:
+    """int64 [ng, Q, 7]: the pair records of one host partition (every group
+    has rows). Per group two passes in f64: the means (corrected once, as in
+    `_host_group_records`), then the squared deviations and co-deviations."""
+    out = np.zeros((ng, len(xs), _PFIELDS), dtype=np.int64)
+    order = np.argsort(ids, kind="stable")
+    counts = np.bincount(ids, minlength=ng).astype(np.int64)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    nf = counts.astype(np.float64)
+
+    def centred(v):
+        x = v.detach().contiguous().numpy()[order].astype(np.float64)
+        mean = np.add.reduceat(x, starts) / nf
+        mean = mean + np.add.reduceat(x - np.repeat(mean, counts), starts) / nf
+        return x, mean, x - np.repeat(mean, counts)
+
+    for q, (vx, vy) in enumerate(zip(xs, ys)):
+        with np.errstate(all="ignore"):
+            x, mx, dx = centred(vx)
+            y, my, dy = centred(vy)
+            f = _f64(out[:, q, :_PBAD])
+            f[:, _PN], f[:, _PMX], f[:, _PMY] = nf, mx, my
+            f[:, _PM2X] = np.add.reduceat(dx * dx, starts)
+            f[:, _PM2Y] = np.add.reduceat(dy * dy, starts)
+            f[:, _PC] = np.add.reduceat(dx * dy, starts)
+        out[:, q, _PBAD] = np.add.reduceat((~(np.isfinite(x) & np.isfinite(y))).astype(np.int64), starts)
+    return out
+
+
+def _pair_chan(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Chan's merge of pair records [s, Q, 7], `a` the earlier rows (the
+    arithmetic of kernels/moments.h merge_pairs, without its contractions)."""
+    r = np.empty_like(a)
+    fa, fb, fr = _f64(a[..., :_PBAD]), _f64(b[..., :_PBAD]), _f64(r[..., :_PBAD])
+    an, bn = fa[..., _PN], fb[..., _PN]
+    with np.errstate(all="ignore"):
+        n = an + bn
+        dx, dy = fb[..., _PMX] - fa[..., _PMX], fb[..., _PMY] - fa[..., _PMY]
+        f = np.where(n > 0, bn / np.where(n > 0, n, 1.0), 0.0)
+
+        def pick(j, merged):
+            return np.where(an == 0, fb[..., j], np.where(bn == 0, fa[..., j], merged))
+        fr[..., _PN] = n
+        fr[..., _PMX] = pick(_PMX, fa[..., _PMX] + dx * f)
+        fr[..., _PMY] = pick(_PMY, fa[..., _PMY] + dy * f)
+        fr[..., _PM2X] = pick(_PM2X, fa[..., _PM2X] + fb[..., _PM2X] + dx * dx * (an * f))
+        fr[..., _PM2Y] = pick(_PM2Y, fa[..., _PM2Y] + fb[..., _PM2Y] + dy * dy * (an * f))
+        fr[..., _PC] = pick(_PC, fa[..., _PC] + fb[..., _PC] + dx * dy * (an * f))
+    r[..., _PBAD] = a[..., _PBAD] + b[..., _PBAD]
+    return r
+
+
+def _merge_pair_records(recs: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+    """`_merge_records` for pair records [m, Q, 7] (every group has a record)."""
+    recs = np.ascontiguousarray(recs)
+    counts = np.diff(offsets)
+    out = recs[offsets[:-1]].copy()
+    for j in range(1, int(counts.max()) if len(counts) else 0):
+        sel = np.nonzero(counts > j)[0]
+        out[sel] = _pair_chan(out[sel], recs[offsets[sel] + j])
+    return out
+
+
+def _pair_results(recs: np.ndarray, pairs: Sequence[int], stats: Sequence[str]) -> List[np.ndarray]:
+    """Merged pair records [ng, Q, 7] -> one float64 column per output (the
+    host form of `_C.pair_results`): covar_pop = C / n, covar_samp = C / (n - 1)
+    (NaN below two rows), corr = C / sqrt(M2_x * M2_y) (NaN without rows or
+    where an M2 is 0; not clamped). A group that counts a row with a NaN or an
+    infinity is NaN in all three, whichever row it was."""
+    outs = []
+    for qi, st in zip(pairs, stats):
+        r = np.ascontiguousarray(recs[:, qi, :])
+        f = _f64(r[:, :_PBAD])
+        n, c = f[:, _PN], f[:, _PC]
+        with np.errstate(all="ignore"):
+            if st == "covar_pop":
+                v = np.where(n >= 1, c / np.where(n >= 1, n, 1.0), np.nan)
+            elif st == "covar_samp":
+                v = np.where(n >= 2, c / np.where(n >= 2, n - 1, 1.0), np.nan)
+            elif st == "corr":
+                ok = (n >= 1) & (f[:, _PM2X] != 0) & (f[:, _PM2Y] != 0)
+                v = np.where(ok, c / np.sqrt(np.where(ok, f[:, _PM2X] * f[:, _PM2Y], 1.0)), np.nan)
+            else:
+                raise ValueError(f"'{st}' is not a pair statistic")
+        outs.append(np.asarray(np.where(r[:, _PBAD] > 0, np.nan, v), dtype=np.float64))
+    return outs
+
+
 # ------------------------------------------------------------------ stage 1
-def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_device: bool, what: str):
-    """(distinct key columns of the partition, records [ng, C, 6] int64) of
-    one non-empty partition, on the device or on the host."""
+def _columns_of(specs: Sequence[_Spec], what: str) -> Tuple[List[str], List[Tuple[str, str]]]:
+    """(distinct value columns of the one-column outputs, distinct ordered
+    pairs of the pair outputs), each in order of first use."""
+    vcols: List[str] = []
+    pairs: List[Tuple[str, str]] = []
+    for s in specs:
+        if s.pair is not None:
+            if s.pair not in pairs:
+                pairs.append(s.pair)
+        elif s.column is not None and s.column not in vcols:
+            vcols.append(s.column)
+    if len(vcols) > _MAX_COLS:
+        raise ValueError(f"{what}: at most {_MAX_COLS} distinct value columns per call, got {len(vcols)}; split the "
+                         f"call and join the results on the keys")
+    if len(pairs) > _MAX_COLS:
+        raise ValueError(f"{what}: at most {_MAX_COLS} distinct column pairs per call, got {len(pairs)}; split the "
+                         f"call and join the results on the keys")
+    return vcols, pairs
+
+
+def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_device: bool, what: str,
+                       pairs: Sequence[Tuple[str, str]] = (), single: bool = True):
+    """(distinct key columns of the partition, records [ng, C, 6] int64, pair
+    records [ng, Q, 7] int64) of one non-empty partition, on the device or on
+    the host; a kind the call does not need (`single` False, no `pairs`) is
+    None."""
     from .. import core, engine
     from .._native import _C
     from ..ops import groupby as G
     from ..utils.logging import metrics
     dev = engine.compute_device() if on_device else torch.device("cpu")
-    vals = [_scalar_column(b, v, what).to(dev) for v in vcols]
-    if not vals:  # only rows are counted: a column of zeros carries n
+    vals = [_scalar_column(b, v, what).to(dev) for v in vcols] if single else []
+    if single and not vals:  # only rows are counted: a column of zeros carries n
         vals = [engine.device_full(b.nrows, 0, torch.uint8, dev)]
+    xs = [_scalar_column(b, x, what).to(dev) for x, _ in pairs]
+    ys = [_scalar_column(b, y, what).to(dev) for _, y in pairs]
     if keys:
         K = [b.columns[k] for k in keys]
         if not G.device_keys(K):
@@ -248,19 +383,66 @@ def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_d
         ids, uniq, ng = G.group_ids([k.to(dev).contiguous() for k in K])
     else:
         ids, uniq, ng = engine.device_full(b.nrows, 0, torch.int64, dev), [], 1
+    recs = precs = None
     if on_device:
         perm, offsets = _C.segment_csr(ids, ng)
-        recs = _C.group_moments([v.contiguous() for v in vals], perm, offsets)
-        metrics.add("group_agg_device_partitions")
+        vals, xs, ys = ([v.contiguous() for v in vs] for vs in (vals, xs, ys))
+        if vals and xs:  # (the work items of the segments are built once for both)
+            recs, precs = _C.group_both_moments(vals, xs, ys, perm, offsets)
+        elif vals:
+            recs = _C.group_moments(vals, perm, offsets)
+        else:
+            precs = _C.group_pair_moments(xs, ys, perm, offsets)
     else:
-        recs = torch.from_numpy(_host_group_records(vals, ids.numpy(), ng))
-        metrics.add("group_agg_host_partitions")
-    metrics.add("group_agg_rows", b.nrows * len(vals))
-    return uniq, recs
+        if vals:
+            recs = torch.from_numpy(_host_group_records(vals, ids.numpy(), ng))
+        if xs:
+            precs = torch.from_numpy(_host_pair_records(xs, ys, ids.numpy(), ng))
+    where = "device" if on_device else "host"
+    if vals:
+        metrics.add(f"group_agg_{where}_partitions")
+        metrics.add("group_agg_rows", b.nrows * len(vals))
+    if xs:
+        metrics.add(f"pair_agg_{where}_partitions")
+        metrics.add("pair_agg_rows", b.nrows * len(xs))
+    return uniq, recs, precs
 
 
-def _needed(keys, vcols):
-    return list(keys) + [v for v in vcols if v not in keys]
+def _needed(keys, vcols, pairs=()):
+    out = list(keys)
+    for v in list(vcols) + [c for p in pairs for c in p]:
+        if v not in out:
+            out.append(v)
+    return out
+
+
+def _outputs(specs, scol, spair, vdt, merged, pmerged, on_device: bool) -> List[torch.Tensor]:
+    """One column per output from the merged records [ng, C, 6] and pair
+    records [ng, Q, 7], in the order of `specs`."""
+    from .._native import _C
+    one = [i for i, s in enumerate(specs) if s.pair is None]
+    two = [i for i, s in enumerate(specs) if s.pair is not None]
+    outs: List[Any] = [None] * len(specs)
+    for a in range(0, len(one), _MAX_COLS):
+        at = one[a:a + _MAX_COLS]
+        cols, fns = [scol[i] for i in at], [specs[i].fn for i in at]
+        if on_device:
+            got = _C.group_results(merged.contiguous(), cols, fns, [vdt[c] for c in cols])
+        else:
+            np_dt = [torch.empty(0, dtype=vdt[c]).numpy().dtype for c in cols]
+            got = [torch.from_numpy(np.ascontiguousarray(o)) for o in _host_results(merged.numpy(), cols, fns, np_dt)]
+        for i, o in zip(at, got):
+            outs[i] = o
+    for a in range(0, len(two), _MAX_COLS):
+        at = two[a:a + _MAX_COLS]
+        prs, fns = [spair[i] for i in at], [specs[i].fn for i in at]
+        if on_device:
+            got = _C.pair_results(pmerged.contiguous(), prs, fns)
+        else:
+            got = [torch.from_numpy(np.ascontiguousarray(o)) for o in _pair_results(pmerged.numpy(), prs, fns)]
+        for i, o in zip(at, got):
+            outs[i] = o
+    return outs
 
 
 # ------------------------------------------------------------------ keyed
@@ -275,20 +457,18 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
     if not keys:
         return frame_agg(df, specs, what)
     _check_keys(df, keys, what)
-    vcols: List[str] = []
-    for s in specs:
-        if s.column is not None and s.column not in vcols:
-            vcols.append(s.column)
-    if len(vcols) > _MAX_COLS:
-        raise ValueError(f"{what}: at most {_MAX_COLS} distinct value columns per call, got {len(vcols)}; split the "
-                         f"call and join the results on the keys")
-    C = max(len(vcols), 1)
-    vdt = [D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]
+    vcols, pairs = _columns_of(specs, what)
+    single = any(s.pair is None for s in specs)
+    C = max(len(vcols), 1) if single else 0
+    Q = len(pairs)
+    W1, W = C * _FIELDS, C * _FIELDS + Q * _PFIELDS  # a group's row: its records, then its pair records
+    vdt = ([D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]) if single else []
     is_float = [t.is_floating_point for t in vdt]
     kdt = [D.torch_dtype(_tf_dtype(df, k)) for k in keys]
-    out_dt = [_aggregate_dtype(df, s.fn, s.column) for s in specs]
+    out_dt = [torch.float64 if s.pair is not None else _aggregate_dtype(df, s.fn, s.column) for s in specs]
     scol = [vcols.index(s.column) if s.column is not None else 0 for s in specs]
-    needed = _needed(keys, vcols)
+    spair = [pairs.index(s.pair) if s.pair is not None else 0 for s in specs]
+    needed = _needed(keys, vcols, pairs)
     keep_on_device = any(b.columns[n].is_cuda for b in (df._cached or {}).values() if b.nrows for n in needed
                          if isinstance(b.columns[n], torch.Tensor))
     world = max(1, dist.world_size())
@@ -309,17 +489,29 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
             return empty()
         on_device = engine.gpu_available() and not int(flags[0])
         dev = engine.compute_device() if on_device else torch.device("cpu")
-        got = [(pid,) + _partition_records(b, keys, vcols, on_device, what) for pid, b in parts]
+        got = []
+        for pid, b in parts:
+            u, r, pr = _partition_records(b, keys, vcols, on_device, what, pairs, single)
+            ng = int((r if r is not None else pr).shape[0])
+            row = [t.reshape(ng, -1) for t in (r, pr) if t is not None]
+            got.append((pid, u, row[0] if len(row) == 1 else torch.cat(row, dim=1)))
         if got:
             K = [engine.cat_rows([u[j] for _, u, _ in got]) for j in range(len(keys))]
-            R = engine.cat_rows([r.reshape(r.shape[0], C * _FIELDS) for _, _, r in got])
+            R = engine.cat_rows([r for _, _, r in got])
             pids = engine.cat_rows([engine.device_full(r.shape[0], pid, torch.int64, dev) for pid, _, r in got])
         else:
             K = [engine.device_empty(0, t, dev) for t in kdt]
-            R = engine.device_empty((0, C * _FIELDS), torch.int64, dev)
+            R = engine.device_empty((0, W), torch.int64, dev)
             pids = engine.device_empty(0, torch.int64, dev)
+
+        def split(rows):
+            """rows [m, W] -> (records [m, C, 6], pair records [m, Q, 7]); a kind without columns is None"""
+            m = int(rows.shape[0])
+            return (rows[:, :W1].contiguous().reshape(m, C, _FIELDS) if C else None,
+                    rows[:, W1:].contiguous().reshape(m, Q, _PFIELDS) if Q else None)
         if not dist.is_distributed() and len(got) == 1:
-            ukeys, merged = K, R.reshape(-1, C, _FIELDS)  # one partition: its records are the result
+            ukeys = K
+            merged, pmerged = split(R)  # one partition: its records are the result
         else:
             if dist.is_distributed():
                 recv = G.route(K, [pids, R])
@@ -332,29 +524,28 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
             ids, uniq, m2 = G.group_ids([k.contiguous() for k in K] + [pids])
             if m2 != m:
                 raise RuntimeError(f"{what}: {m} records but {m2} distinct (key, partition) pairs")
-            ordered = engine.device_empty((m, C * _FIELDS), torch.int64, dev)
+            ordered = engine.device_empty((m, W), torch.int64, dev)
             if on_device:
                 _C.scatter_rows(ordered, ids, R.contiguous())
             else:
                 ordered[ids] = R
             ids2, ukeys, ng = G.group_ids([u.contiguous() for u in uniq[:-1]])
+            recs, precs = split(ordered)
+            merged = pmerged = None
             if on_device:
                 _, offsets = _C.segment_csr(ids2, ng)
-                merged = _C.merge_group_records(ordered.reshape(m, C, _FIELDS), offsets, is_float)
+                if C:
+                    merged = _C.merge_group_records(recs, offsets, is_float)
+                if Q:
+                    pmerged = _C.merge_pair_records(precs, offsets)
             else:
                 offsets = np.concatenate([[0], np.cumsum(np.bincount(ids2.numpy(), minlength=ng))]).astype(np.int64)
-                merged = torch.from_numpy(_merge_records(ordered.numpy().reshape(m, C, _FIELDS), offsets, is_float))
-        ng = int(merged.shape[0])
-        outs: List[torch.Tensor] = []
-        for a in range(0, len(specs), _MAX_COLS):
-            sl = slice(a, a + _MAX_COLS)
-            if on_device:
-                outs.extend(_C.group_results(merged.contiguous(), scol[sl], [s.fn for s in specs[sl]],
-                                             [vdt[c] for c in scol[sl]]))
-            else:
-                np_dt = [torch.empty(0, dtype=vdt[c]).numpy().dtype for c in scol[sl]]
-                outs.extend(torch.from_numpy(np.ascontiguousarray(o)) for o in
-                            _host_results(merged.numpy(), scol[sl], [s.fn for s in specs[sl]], np_dt))
+                if C:
+                    merged = torch.from_numpy(_merge_records(recs.numpy(), offsets, is_float))
+                if Q:
+                    pmerged = torch.from_numpy(_merge_pair_records(precs.numpy(), offsets))
+        ng = int((merged if merged is not None else pmerged).shape[0])
+        outs = _outputs(specs, scol, spair, vdt, merged, pmerged, on_device)
         keep = on_device and keep_on_device
         cols: Dict[str, Any] = {k: (u if keep else u.cpu()) for k, u in zip(keys, ukeys)}
         cols.update({s.name: (o if keep else o.cpu()) for s, o in zip(specs, outs)})
@@ -374,40 +565,65 @@ def frame_agg(df, specs, what: str = "agg"):
     from .dataframe import from_columns
     if not isinstance(specs, list) or not all(isinstance(s, _Spec) for s in specs):
         specs = _specs(df, [], list(specs), what)
-    vcols: List[str] = []
-    for s in specs:
-        if s.column is not None and s.column not in vcols:
-            vcols.append(s.column)
-    if len(vcols) > _MAX_COLS:
-        raise ValueError(f"{what}: at most {_MAX_COLS} distinct value columns per call, got {len(vcols)}")
-    C = max(len(vcols), 1)
-    vdt = [D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]
+    vcols, pairs = _columns_of(specs, what)
+    single = any(s.pair is None for s in specs)
+    C = max(len(vcols), 1) if single else 0
+    Q = len(pairs)
+    W1, W = C * _FIELDS, C * _FIELDS + Q * _PFIELDS
+    vdt = ([D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]) if single else []
     is_float = [t.is_floating_point for t in vdt]
     scol = [vcols.index(s.column) if s.column is not None else 0 for s in specs]
+    spair = [pairs.index(s.pair) if s.pair is not None else 0 for s in specs]
+    pcols = _needed([], [], pairs)
 
     def run():
         from .. import engine
+        from .._native import _C
+        from ..utils.logging import metrics
         blocks = df._blocks()
-        table = torch.zeros((df.num_partitions, C, _FIELDS), dtype=torch.int64)
+        # a partition's row: its records [C, 6], then its pair records [Q, 7]
+        table = torch.zeros((df.num_partitions, W), dtype=torch.int64)
         for pid in sorted(blocks):
             b = blocks[pid]
-            if b.nrows:
+            if not b.nrows:
+                continue
+            if single:
                 on_device = engine.gpu_available() and _block_on_device(b, vcols) and bool(vcols)
-                table[pid] = _partition_records(b, [], vcols, on_device, what)[1].cpu()[0]
+                table[pid, :W1] = _partition_records(b, [], vcols, on_device, what)[1].cpu()[0].reshape(-1)
+            if not Q:
+                continue
+            if engine.gpu_available() and _block_on_device(b, pcols):
+                # read where it is, densely: no CSR of one segment, no gather
+                xs = [_scalar_column(b, x, what).contiguous() for x, _ in pairs]
+                ys = [_scalar_column(b, y, what).contiguous() for _, y in pairs]
+                table[pid, W1:] = _C.column_pair_moments(xs, ys).cpu().reshape(-1)
+                metrics.add("pair_agg_device_partitions")
+                metrics.add("pair_agg_rows", b.nrows * Q)
+            else:
+                table[pid, W1:] = _partition_records(b, [], [], False, what, pairs, False)[2][0].reshape(-1)
         dist.all_reduce_host_(table, "Sum")  # (every rank fills the rows of its own partitions; the others are zero)
         return table.numpy()
-    table = dist.agreed(what, run)
-    recs = table[_f64(np.ascontiguousarray(table[:, 0, _N])) > 0]  # the partitions with rows, in partition order
-    if len(recs):
-        merged = _merge_records(recs, np.array([0, len(recs)], dtype=np.int64), is_float)
+    table = np.ascontiguousarray(dist.agreed(what, run))
+    # the partitions with rows, in partition order (n is the first field of both record kinds)
+    table = table[_f64(np.ascontiguousarray(table[:, 0])) > 0]
+    recs = np.ascontiguousarray(table[:, :W1]).reshape(-1, C, _FIELDS) if C else None
+    precs = np.ascontiguousarray(table[:, W1:]).reshape(-1, Q, _PFIELDS) if Q else None
+    merged = pmerged = None
+    if len(table):
+        whole = np.array([0, len(table)], dtype=np.int64)
+        if C:
+            merged = _merge_records(recs, whole, is_float)
+        if Q:
+            pmerged = _merge_pair_records(precs, whole)
     else:
         for s in specs:
             if s.fn in ("min", "max"):
                 raise ValueError(f"{what}: {s.fn}({s.column}) of a frame without rows does not exist")
-        merged = np.zeros((1, C, _FIELDS), dtype=np.int64)
-    np_dt = [torch.empty(0, dtype=vdt[c]).numpy().dtype for c in scol]
-    outs = _host_results(merged, scol, [s.fn for s in specs], np_dt)
-    return from_columns({s.name: np.ascontiguousarray(o) for s, o in zip(specs, outs)}, num_partitions=1)
+        merged = np.zeros((1, C, _FIELDS), dtype=np.int64) if C else None
+        pmerged = np.zeros((1, Q, _PFIELDS), dtype=np.int64) if Q else None
+    outs = _outputs(specs, scol, spair, vdt, torch.from_numpy(merged) if C else None,
+                    torch.from_numpy(pmerged) if Q else None, False)
+    return from_columns({s.name: np.ascontiguousarray(o.numpy()) for s, o in zip(specs, outs)}, num_partitions=1)
 
 
 # ------------------------------------------------------------------ shortcuts

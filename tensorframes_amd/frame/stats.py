@@ -355,3 +355,24 @@ class DataFrameStatFunctions:
         return approx_quantile(self.df, col, probabilities, relativeError)
 
     approx_quantile = approxQuantile
+
+    def corr(self, col1, col2, method="pearson"):
+        return _pair_statistic(self.df, "corr", col1, col2, method)
+
+    def cov(self, col1, col2):
+        return _pair_statistic(self.df, "covar_samp", col1, col2, "pearson")
+
+
+def _pair_statistic(df, fn: str, col1, col2, method) -> float:
+    """`df.stat.corr` / `df.stat.cov`: `DataFrame.agg` of one pair expression,
+    as a Python float (an action, and collective)."""
+    from .. import functions as F
+    from .group_agg import frame_agg
+    what = "corr" if fn == "corr" else "cov"
+    if method != "pearson":
+        raise ValueError(f"{what}: only the 'pearson' method is supported, got {method!r}")
+    for c in (col1, col2):
+        if not isinstance(c, str):
+            raise TypeError(f"{what}: column names are expected, got {type(c).__name__}")
+    out = frame_agg(df, [getattr(F, fn)(col1, col2).alias(what)], what)
+    return float(out.to_numpy(what)[0])

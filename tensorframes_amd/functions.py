@@ -5,8 +5,10 @@
 
 Each function takes a column name or a plain column reference (`tfs.col("x")`,
 `df["x"]`) and returns an `AggregateExpression`; `.alias(name)` renames its
-output column. These reduce a column over the rows of a group. They are not
-`Column.sum()` and friends, which reduce the cell of one row.
+output column. `corr`, `covar_samp` and `covar_pop` take two columns and return
+a `PairAggregateExpression`, accepted wherever the others are. These reduce a
+column over the rows of a group. They are not `Column.sum()` and friends,
+which reduce the cell of one row.
 """
 from __future__ import annotations
 
@@ -14,8 +16,9 @@ from typing import Optional
 
 from .frame.column import Column
 
-__all__ = ["AggregateExpression", "count", "sum", "avg", "mean", "min", "max", "stddev", "stddev_samp", "stddev_pop",
-           "variance", "var_samp", "var_pop", "row_number", "rank", "dense_rank"]
+__all__ = ["AggregateExpression", "PairAggregateExpression", "count", "sum", "avg", "mean", "min", "max", "stddev",
+           "stddev_samp", "stddev_pop", "variance", "var_samp", "var_pop", "corr", "covar_samp", "covar_pop",
+           "row_number", "rank", "dense_rank"]
 
 # the canonical statistic behind every accepted name (the dict form of agg uses the same table)
 FUNCTIONS = {
@@ -64,6 +67,39 @@ class AggregateExpression:
         return f"AggregateExpression<{self.output_name}>"
 
 
+class PairAggregateExpression:
+    """One aggregate of two columns read together: `fn` is corr, covar_samp or
+    covar_pop, `x` and `y` the value columns' names. The output is float64."""
+
+    __slots__ = ("fn", "x", "y", "_alias")
+
+    def __init__(self, fn: str, x: str, y: str, alias: Optional[str] = None):
+        self.fn = fn
+        self.x = x
+        self.y = y
+        self._alias = alias
+
+    def alias(self, name: str) -> "PairAggregateExpression":
+        if not isinstance(name, str) or not name:
+            raise TypeError(f"alias: a non-empty column name is expected, got {name!r}")
+        return PairAggregateExpression(self.fn, self.x, self.y, name)
+
+    name = alias
+
+    @property
+    def output_name(self) -> str:
+        if self._alias is not None:
+            return self._alias
+        return f"{self.fn}({self.x}, {self.y})"
+
+    def over(self, spec):
+        raise NotImplementedError(f"{self.fn}({self.x}, {self.y}).over: pair aggregates are not supported over a "
+                                  f"window; count, sum, avg, min and max are")
+
+    def __repr__(self):
+        return f"PairAggregateExpression<{self.output_name}>"
+
+
 class RankingFunction:
     """`row_number()`, `rank()` or `dense_rank()` before its `.over(spec)`."""
 
@@ -88,10 +124,15 @@ def _make(fn: str, col) -> AggregateExpression:
                             f"{fn}(name)")
         if col.sort_order is not None:
             raise TypeError(f"{fn}: '{col.output_name}.{col.sort_order}()' is a sort order, not a column")
-        return AggregateExpression(FUNCTIONS[fn], col._expr[1])
+        return AggregateExpression(FUNCTIONS.get(fn, fn), col._expr[1])
     if not isinstance(col, str):
         raise TypeError(f"{fn}: a column name or a column reference is expected, got {type(col).__name__}")
-    return AggregateExpression(FUNCTIONS[fn], col)
+    return AggregateExpression(FUNCTIONS.get(fn, fn), col)
+
+
+def _make_pair(fn: str, col1, col2) -> PairAggregateExpression:
+    # (the rules, and the errors, of the one-column functions for each argument)
+    return PairAggregateExpression(fn, _make(fn, col1).column, _make(fn, col2).column)
 
 
 def count(col) -> AggregateExpression:
@@ -150,6 +191,25 @@ def var_samp(col) -> AggregateExpression:
 
 def var_pop(col) -> AggregateExpression:
     return _make("var_pop", col)
+
+
+def corr(col1, col2) -> PairAggregateExpression:
+    """Pearson's correlation coefficient of two columns, C / sqrt(M2_x * M2_y)
+    with C the sum of (x - mean_x)(y - mean_y): NaN for a group without rows or
+    with a constant column (one row included), and for a group with a NaN or
+    an infinity in either column. Not clamped, as in Spark: a value such as
+    1.0000000000000002 can occur."""
+    return _make_pair("corr", col1, col2)
+
+
+def covar_samp(col1, col2) -> PairAggregateExpression:
+    """The sample covariance C / (n - 1) (NaN for a group of one row)."""
+    return _make_pair("covar_samp", col1, col2)
+
+
+def covar_pop(col1, col2) -> PairAggregateExpression:
+    """The population covariance C / n."""
+    return _make_pair("covar_pop", col1, col2)
 
 
 def row_number() -> RankingFunction:
