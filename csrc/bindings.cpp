@@ -1688,6 +1688,70 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     }
     return py::cast(host_tensor_to_at(t));
   });
+  // Which kernels a reduction takes: the host-side routing of kernels/reduce.hip
+  // (no device needed). The tests pin every case to the route it was written for.
+  auto route_dtype = [](const std::string& name) {
+    for (DType d : {DType::F32, DType::F64, DType::I32, DType::I64, DType::BOOL})
+      if (name == dtype_name(d)) return d;
+    TFA_CHECK(false, "reduce route: dtype ", name, " not supported (float32, float64, int32, int64, bool)");
+    return DType::INVALID;
+  };
+  auto route_redop = [](const std::string& op) {
+    k::RedOp rop = op == "Sum" ? k::RedOp::SUM : op == "Min" ? k::RedOp::MIN : op == "Max" ? k::RedOp::MAX
+                 : op == "Prod" ? k::RedOp::PROD : k::RedOp::ALL;
+    TFA_CHECK(rop != k::RedOp::ALL, "unsorted segment route: unsupported op ", op);
+    return rop;
+  };
+  m.def("reduce_route", [route_dtype](const std::string& dtype, int64_t outer, int64_t r, int64_t inner, bool aligned16) {
+    TFA_CHECK(outer > 0 && r > 0 && inner > 0, "reduce_route: outer, r and inner must be positive");
+    return std::string(k::reduce_route_name(k::reduce_route(route_dtype(dtype), outer, r, inner, aligned16).route));
+  }, py::arg("dtype"), py::arg("outer"), py::arg("r"), py::arg("inner"), py::arg("aligned16") = true,
+     "name of the kernel route k::reduce takes for x viewed as [outer, r, inner]");
+  m.def("reduce_route_info", [route_dtype](const std::string& dtype, int64_t outer, int64_t r, int64_t inner, bool aligned16) {
+    TFA_CHECK(outer > 0 && r > 0 && inner > 0, "reduce_route: outer, r and inner must be positive");
+    const DType dt = route_dtype(dtype);
+    k::ReducePlan p = k::reduce_route(dt, outer, r, inner, aligned16);
+    py::dict d;
+    d["route"] = std::string(k::reduce_route_name(p.route));
+    d["S"] = p.S;
+    d["rows_per_split"] = p.rows_per_split;
+    d["fold"] = p.fold;
+    d["col_blocks"] = p.col_blocks;
+    d["vec"] = p.vec;
+    d["workspace_bytes"] = k::reduce_workspace_bytes(dt, outer, r, inner);
+    return d;
+  }, py::arg("dtype"), py::arg("outer"), py::arg("r"), py::arg("inner"), py::arg("aligned16") = true);
+  m.def("reduce_route_names", [] {
+    std::vector<std::string> v;
+    for (int i = 0; i < (int)k::RedRoute::COUNT; ++i) v.push_back(k::reduce_route_name((k::RedRoute)i));
+    return v;
+  }, "every name reduce_route can return");
+  m.def("unsorted_segment_route", [route_dtype, route_redop](const std::string& op, const std::string& dtype, int64_t n,
+                                                             int64_t inner, int64_t nseg) {
+    TFA_CHECK(n > 0 && inner > 0 && nseg > 0, "unsorted_segment_route: n, inner and nseg must be positive");
+    return k::unsorted_segment_route_name(k::unsorted_segment_route(route_redop(op), route_dtype(dtype), n, inner, nseg));
+  }, py::arg("op"), py::arg("dtype"), py::arg("n"), py::arg("inner"), py::arg("nseg"),
+     "route of k::unsorted_segment_reduce: tiny_int, small_int, private_g<G>, sorted_perm_p<inner_pad>, sorted_perm_wide");
+  m.def("unsorted_segment_route_info", [route_dtype, route_redop](const std::string& op, const std::string& dtype,
+                                                                  int64_t n, int64_t inner, int64_t nseg) {
+    TFA_CHECK(n > 0 && inner > 0 && nseg > 0, "unsorted_segment_route: n, inner and nseg must be positive");
+    k::UsegPlan p = k::unsorted_segment_route(route_redop(op), route_dtype(dtype), n, inner, nseg);
+    py::dict d;
+    d["route"] = k::unsorted_segment_route_name(p);
+    d["B"] = p.B;
+    d["G"] = p.G;
+    d["tile"] = p.tile;
+    d["rows_per_block"] = p.rows_per_block;
+    d["inner_pad"] = p.inner_pad;
+    return d;
+  }, py::arg("op"), py::arg("dtype"), py::arg("n"), py::arg("inner"), py::arg("nseg"));
+  m.def("unsorted_segment_route_names", [] {
+    std::vector<std::string> v{"tiny_int", "small_int"};
+    for (int g = 1; g <= 64; g <<= 1) v.push_back("private_g" + std::to_string(g));
+    for (int p = 1; p <= 64; p <<= 1) v.push_back("sorted_perm_p" + std::to_string(p));
+    v.push_back("sorted_perm_wide");
+    return v;
+  }, "every name unsorted_segment_route can return");
   // Segmented reduction over rows sorted by segment (CSR offsets, int64):
   // the groupBy/aggregate monoid fast path. Device tensors run the HIP
   // kernel; host tensors the ATen reference.
@@ -1705,17 +1769,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     osz[0] = nseg;
     const int64_t nrows = x.size(0);
     if (!x.is_cuda()) {
-      at::Tensor xs = x.reshape({nrows, -1});
-      at::Tensor is = ids.to(at::kLong);
+      // the device kernels' rules: ids outside [0, nseg) are dropped, a segment
+      // starts from the op's identity (Min / Max: the dtype's max() / lowest())
+      int64_t cols = 1;
+      for (int64_t i = 1; i < x.dim(); ++i) cols *= x.size(i);
+      at::Tensor il = ids.to(at::kLong);
+      at::Tensor valid = (il >= 0) & (il < nseg);
+      at::Tensor xs = x.reshape({nrows, cols}).index({valid});
+      at::Tensor is = il.index({valid});
       at::Tensor out;
       if (rop == k::RedOp::SUM) {
-        out = at::zeros({nseg, xs.size(1)}, x.options()).index_add_(0, is, xs);
+        out = at::zeros({nseg, cols}, x.options()).index_add_(0, is, xs);
       } else if (rop == k::RedOp::PROD) {
-        out = at::ones({nseg, xs.size(1)}, x.options()).index_reduce_(0, is, xs, "prod", true);
+        out = at::ones({nseg, cols}, x.options()).index_reduce_(0, is, xs, "prod", true);
       } else {
         const bool mx = rop == k::RedOp::MAX;
-        out = at::empty({nseg, xs.size(1)}, x.options());
-        out = out.index_reduce_(0, is, xs, mx ? "amax" : "amin", false);
+        at::Scalar init;
+        bool known = true;
+        switch (x.scalar_type()) {
+          case at::kInt: init = mx ? std::numeric_limits<int32_t>::lowest() : std::numeric_limits<int32_t>::max(); break;
+          case at::kLong: init = mx ? std::numeric_limits<int64_t>::lowest() : std::numeric_limits<int64_t>::max(); break;
+          case at::kFloat: init = mx ? std::numeric_limits<float>::lowest() : std::numeric_limits<float>::max(); break;
+          case at::kDouble: init = mx ? std::numeric_limits<double>::lowest() : std::numeric_limits<double>::max(); break;
+          default: known = false;  // a dtype the device kernels do not take: every segment must have a row
+        }
+        out = known ? at::full({nseg, cols}, init, x.options()) : at::empty({nseg, cols}, x.options());
+        out = out.index_reduce_(0, is, xs, mx ? "amax" : "amin", known);
       }
       out = out.reshape(osz).contiguous();
       if (out_opt) return out_opt->copy_(out);

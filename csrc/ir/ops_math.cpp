@@ -283,6 +283,16 @@ OpDef make_reduce(k::RedOp op) {
     std::vector<int64_t> axes = norm_axes(c.host_ivalue(1), std::max<int64_t>(x.dim(), 1));
     if (x.dim() == 0) axes.clear();
     bool keep = keep_dims(c.node);
+    // an empty reduced axis, the same on host and device: Sum 0, Prod 1, All
+    // true, Any false, float Mean NaN; Min, Max and an integer Mean have no value
+    int64_t reduced = 1;
+    for (auto a : axes) reduced *= x.size(a);
+    if (!axes.empty() && reduced == 0) {
+      const bool no_value = op == k::RedOp::MIN || op == k::RedOp::MAX ||
+                            (op == k::RedOp::MEAN && !at::isFloatingType(x.scalar_type()));
+      TFA_CHECK(!no_value, c.node.op, " '", c.node.name, "': reduction over an empty axis has no value (",
+                dtype_name(c.out_dtype()), " input of ", x.dim(), " dimensions, ", axes.size(), " reduced)");
+    }
     if (!c.gpu) {
       at::Tensor r = cpu_reduce(op, x, axes, keep);
       if (op == k::RedOp::ALL || op == k::RedOp::ANY) r = r.to(at::kBool);
@@ -587,7 +597,10 @@ void register_math_ops(OpRegistry& r) {
       at::Tensor x = c.input(0), ids = c.input(1);
       int64_t nseg = c.host_ivalue(2)[0];
       int64_t nrows = ids.numel();
-      int64_t inner = nrows ? x.numel() / nrows : 0;
+      // the columns of one row: known from the shape even when there are no rows
+      // (every segment is then empty and gets the op's identity)
+      int64_t inner = 1;
+      for (int64_t i = ids.dim(); i < x.dim(); ++i) inner *= x.size(i);
       if (!c.gpu) {
         at::Tensor xf = x.reshape({nrows, inner});
         at::Tensor idl = ids.reshape({-1}).to(at::kLong);

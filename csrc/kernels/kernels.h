@@ -59,6 +59,24 @@ enum class RedOp : int { SUM, PROD, MIN, MAX, MEAN, ALL, ANY };
 size_t reduce_workspace_bytes(DType dt, int64_t outer, int64_t r, int64_t inner);
 void reduce(RedOp op, DType dt, const void* x, void* y, int64_t outer, int64_t r, int64_t inner,
             void* workspace, hipStream_t s);
+// The kernels one reduce() launch takes: plain host code, no device. reduce()
+// and reduce_workspace_bytes() switch on this (the routing is written once)
+// and the tests read it to know which kernel a shape lands on.
+enum class RedRoute : int {
+  ROW_WAVE_VEC, ROW_WAVE, ROW_BLOCK, ROW_SPLIT, ROW_SPLIT_FOLD,
+  COL, COL_VEC, COL_SPLIT, COL_VEC_SPLIT, COL_SPLIT_FOLD, COL_VEC_SPLIT_FOLD, COUNT
+};
+struct ReducePlan {
+  RedRoute route;
+  int64_t S = 1;               // slices of r (partial slabs); 1: the kernel writes y itself
+  int64_t rows_per_split = 0;  // r elements per slice
+  int64_t fold = 0;            // slabs left by the fold pass, 0: no fold pass
+  int64_t col_blocks = 0;      // column path: 256-thread blocks across inner
+  int vec = 1;                 // elements per 16-byte load (1: scalar loads)
+};
+const char* reduce_route_name(RedRoute r);
+// aligned16: whether x is 16-byte aligned (the vector kernels need it)
+ReducePlan reduce_route(DType dt, int64_t outer, int64_t r, int64_t inner, bool aligned16);
 // arg-reduce over r of [outer, r, inner]; out int32 or int64
 void argreduce(bool is_min, DType dt, DType out_dt, const void* x, void* y, int64_t outer,
                int64_t r, int64_t inner, hipStream_t s);
@@ -89,6 +107,20 @@ size_t unsorted_segment_workspace_bytes(RedOp op, DType dt, int64_t n, int64_t i
 void unsorted_segment_reduce(RedOp op, DType dt, DType idt, const void* x, const void* ids,
                              void* y, int64_t n, int64_t inner, int64_t nseg, void* workspace,
                              hipStream_t s);
+// The route of one unsorted_segment_reduce() call (host only, as reduce_route).
+enum class UsegRoute : int { TINY_INT, SMALL_INT, PRIVATE, SORTED_PERM };
+struct UsegPlan {
+  UsegRoute route;
+  int64_t B = 0;             // tiny_int / private: row blocks (partial slabs)
+  int G = 0;                 // private: lanes that share one output element in the final pass
+  int64_t tile = 0;          // private: columns per block
+  int64_t rows_per_block = 0;
+  int inner_pad = 0;         // sorted_perm: inner rounded up to a power of two, at most 64
+  bool wide = false;         // sorted_perm: inner > 64
+};
+UsegPlan unsorted_segment_route(RedOp op, DType dt, int64_t n, int64_t inner, int64_t nseg);
+// "tiny_int", "small_int", "private_g<G>", "sorted_perm_p<inner_pad>" ("sorted_perm_wide" for inner > 64)
+std::string unsorted_segment_route_name(const UsegPlan& p);
 // segmented reduce with CSR offsets over contiguous rows (deterministic)
 void segment_reduce_csr(RedOp op, DType dt, const void* x, const int64_t* offsets, void* y,
                         int64_t nseg, int64_t inner, hipStream_t s);

@@ -44,8 +44,43 @@ template <int OP, typename A>
 __device__ __forceinline__ A combine(A a, A b) {
   if constexpr (OP == (int)RedOp::SUM || OP == (int)RedOp::MEAN) return a + b;
   else if constexpr (OP == (int)RedOp::PROD) return a * b;
-  else if constexpr (OP == (int)RedOp::MIN || OP == (int)RedOp::ALL) return b < a ? b : a;
-  else return b > a ? b : a;
+  else if constexpr (OP == (int)RedOp::MIN || OP == (int)RedOp::ALL) {
+    // float Min/Max propagate NaN (like the host's amin / amax): a NaN on
+    // either side wins, and stays once it is in the accumulator
+    if constexpr (std::is_floating_point<A>::value) return (b < a || b != b) ? b : a;
+    else return b < a ? b : a;
+  } else {
+    if constexpr (std::is_floating_point<A>::value) return (b > a || b != b) ? b : a;
+    else return b > a ? b : a;
+  }
+}
+
+// Total order for arg-reduce and top-k: NaN is the largest value (numpy's and
+// ATen's rule), so ArgMax and TopK put NaN first and ArgMin returns the first
+// NaN as well, like np.argmin. ord_gt(a, b): a is strictly larger than b.
+template <typename T>
+__device__ __forceinline__ bool ord_gt(T a, T b) {
+  if constexpr (std::is_floating_point<T>::value) return a > b || (a != a && b == b);
+  else return a > b;
+}
+template <typename T>
+__device__ __forceinline__ bool ord_eq(T a, T b) {
+  if constexpr (std::is_floating_point<T>::value) return a == b || (a != a && b != b);
+  else return a == b;
+}
+// arg-reduce: does candidate (v, i) beat (best, bi)? ArgMin takes a NaN as the
+// smallest too (np.argmin and at::argmin return the first NaN)
+template <typename T, bool MIN>
+__device__ __forceinline__ bool arg_better(T v, int64_t i, T best, int64_t bi) {
+  if constexpr (MIN && std::is_floating_point<T>::value) {
+    const bool vn = v != v, bn = best != best;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v < best || (v == best && i < bi);
+  } else if constexpr (MIN) {
+    return v < best || (v == best && i < bi);
+  } else {
+    return ord_gt(v, best) || (ord_eq(v, best) && i < bi);
+  }
 }
 
 template <int OP, typename A>
@@ -254,6 +289,7 @@ __global__ __launch_bounds__(256) void col_fold(const typename AccT<T>::type* __
   part2[(int64_t)blockIdx.y * n + i] = acc;
 }
 
+constexpr int64_t kMaxGridY = 65535;  // HIP's limit for grid.y and grid.z
 constexpr int64_t kFoldAbove = 64;  // fold first when more partial slabs than this
 constexpr int64_t kFoldBy = 32;     // slabs per fold thread
 
@@ -273,101 +309,122 @@ void final_pass(typename AccT<T>::type* part, T* y, int64_t n, int64_t S, int64_
   hipLaunchKernelGGL((col_final<T, OP>), dim3(ew_grid(n)), dim3(256), 0, s, part, y, n, S, r);
 }
 
-struct RedPlan {
-  bool row_wave;
-  int64_t S;             // r splits (col path)
-  int64_t col_blocks;
-  int vec;
-};
+}  // namespace
 
-template <typename T>
-RedPlan plan_reduce(int64_t outer, int64_t r, int64_t inner) {
-  RedPlan p{};
-  constexpr int VEC = 16 / sizeof(T) > 0 ? 16 / sizeof(T) : 1;
-  if (inner == 1 && (outer >= 1024 || r <= 4096)) {
-    p.row_wave = true;
+// ---- routing. Every decision between the kernels above is taken here, from
+// the shape, the element size and the pointer's alignment alone.
+const char* reduce_route_name(RedRoute r) {
+  static const char* names[] = {"row_wave_vec", "row_wave", "row_block", "row_split", "row_split_fold",
+                                "col", "col_vec", "col_split", "col_vec_split", "col_split_fold",
+                                "col_vec_split_fold"};
+  return names[(int)r];
+}
+
+ReducePlan reduce_route(DType dt, int64_t outer, int64_t r, int64_t inner, bool aligned16) {
+  ReducePlan p;
+  const int64_t es = dtype_size(dt);
+  const int VEC = (int)(16 / es);
+  if (inner == 1 && (outer >= 1024 || r <= 4096)) {  // one wave per row
+    const bool vec = (r % VEC == 0) && aligned16;
+    p.route = vec ? RedRoute::ROW_WAVE_VEC : RedRoute::ROW_WAVE;
+    p.vec = vec ? VEC : 1;
+    p.rows_per_split = r;
     return p;
   }
-  p.row_wave = false;
-  if (inner == 1) {  // few long rows: split each row over S blocks
-    p.vec = 1;
-    p.col_blocks = 0;
+  if (inner == 1) {
+    // few long rows (outer < 1024, r > 4096): split each row over S >= 2
+    // blocks (2048 / outer >= 2 and r / 1024 >= 4, so S == 1 cannot happen)
     int64_t S = std::max<int64_t>(1, 2048 / std::max<int64_t>(outer, 1));
-    p.S = std::min<int64_t>(std::min<int64_t>(S, std::max<int64_t>(1, r / 1024)), 65535);
+    S = std::min<int64_t>(std::min<int64_t>(S, std::max<int64_t>(1, r / 1024)), 65535);
+    p.rows_per_split = (r + S - 1) / S;
+    p.S = (r + p.rows_per_split - 1) / p.rows_per_split;
+    if (outer <= 64 && r * es <= kBlockRowBytes) {  // one 1024-thread block per row instead
+      p.route = RedRoute::ROW_BLOCK;
+      p.S = 1;
+      p.rows_per_split = r;
+      return p;
+    }
+    p.fold = fold_slabs(p.S);
+    p.route = p.fold ? RedRoute::ROW_SPLIT_FOLD : RedRoute::ROW_SPLIT;
     return p;
   }
-  p.vec = (inner % VEC == 0) ? VEC : 1;
-  int64_t cols = (inner + p.vec - 1) / p.vec;
-  p.col_blocks = (cols + 255) / 256;
-  int64_t blocks = p.col_blocks * outer;
+  const int vec = (inner % VEC == 0) ? VEC : 1;
+  const int64_t vec_blocks = ((inner + vec - 1) / vec + 255) / 256;
+  const int64_t blocks = vec_blocks * outer;
   static const int64_t target = env_positive("TFA_RED_TARGET_BLOCKS", 2048);
   int64_t S = blocks >= target ? 1 : (target + blocks - 1) / blocks;
-  int64_t max_s = std::max<int64_t>(1, r / 64);
-  p.S = std::min<int64_t>(std::min<int64_t>(S, max_s), 65535);
+  S = std::min<int64_t>(std::min<int64_t>(S, std::max<int64_t>(1, r / 64)), 65535);
+  // more outer slices than one grid dimension holds are launched in chunks,
+  // each writing y itself (with the default target S is 1 there anyway)
+  if (outer > kMaxGridY) S = 1;
+  p.rows_per_split = (r + S - 1) / S;
+  p.S = (r + p.rows_per_split - 1) / p.rows_per_split;
+  p.fold = fold_slabs(p.S);
+  const bool use_vec = vec > 1 && aligned16;
+  p.vec = use_vec ? vec : 1;
+  p.col_blocks = use_vec ? vec_blocks : (inner + 255) / 256;
+  if (p.S == 1) p.route = use_vec ? RedRoute::COL_VEC : RedRoute::COL;
+  else if (!p.fold) p.route = use_vec ? RedRoute::COL_VEC_SPLIT : RedRoute::COL_SPLIT;
+  else p.route = use_vec ? RedRoute::COL_VEC_SPLIT_FOLD : RedRoute::COL_SPLIT_FOLD;
   return p;
 }
 
+namespace {
+
 template <typename T, int OP>
-void reduce_typed(const void* xv, void* yv, int64_t outer, int64_t r, int64_t inner, void* ws,
+void reduce_typed(DType dt, const void* xv, void* yv, int64_t outer, int64_t r, int64_t inner, void* ws,
                   hipStream_t s) {
   using A = typename AccT<T>::type;
+  constexpr int VEC = 16 / sizeof(T);
   const T* x = static_cast<const T*>(xv);
   T* y = static_cast<T*>(yv);
-  RedPlan p = plan_reduce<T>(outer, r, inner);
-  if (p.row_wave) {
-    constexpr int VEC = 16 / sizeof(T);
-    bool vec = (r % VEC == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-    int grid = (int)std::min<int64_t>((outer + 3) / 4, 4096);
-    if (vec) hipLaunchKernelGGL((row_reduce_wave<T, OP, VEC>), dim3(grid), dim3(256), 0, s, x, y, outer, r);
-    else hipLaunchKernelGGL((row_reduce_wave<T, OP, 1>), dim3(grid), dim3(256), 0, s, x, y, outer, r);
-    return;
-  }
-  int64_t rows_per_split = (r + p.S - 1) / p.S;
-  int64_t S = (r + rows_per_split - 1) / rows_per_split;
-  if (inner == 1 && S > 1 && outer <= 64 && r * (int64_t)sizeof(T) <= kBlockRowBytes) {
-    hipLaunchKernelGGL((row_reduce_block<T, OP>), dim3((unsigned)outer), dim3(1024), 0, s, x, y, r);
-    return;
-  }
-  if (inner == 1) {
-    TFA_CHECK(ws != nullptr || S == 1, "reduce: missing workspace");
-    TFA_CHECK(outer <= 65535, "reduce: outer dim ", outer, " too large for the split-row path");
-    A* part2 = static_cast<A*>(ws);
-    if (S == 1) {
-      hipLaunchKernelGGL((row_reduce_wave<T, OP, 1>), dim3((unsigned)((outer + 3) / 4)), dim3(256), 0, s, x, y, outer, r);
+  const ReducePlan p = reduce_route(dt, outer, r, inner, (reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  TFA_CHECK(p.S == 1 || ws != nullptr, "reduce: missing workspace");
+  A* part = p.S > 1 ? static_cast<A*>(ws) : nullptr;
+  switch (p.route) {
+    case RedRoute::ROW_WAVE_VEC:
+    case RedRoute::ROW_WAVE: {
+      int grid = (int)std::min<int64_t>((outer + 3) / 4, 4096);
+      if (p.route == RedRoute::ROW_WAVE_VEC)
+        hipLaunchKernelGGL((row_reduce_wave<T, OP, VEC>), dim3(grid), dim3(256), 0, s, x, y, outer, r);
+      else hipLaunchKernelGGL((row_reduce_wave<T, OP, 1>), dim3(grid), dim3(256), 0, s, x, y, outer, r);
       return;
     }
-    hipLaunchKernelGGL((row_split<T, OP>), dim3((unsigned)S, (unsigned)outer), dim3(256), 0, s, x, part2, outer, r,
-                       rows_per_split);
-    final_pass<T, OP>(part2, y, outer, S, r, s);
-    return;
+    case RedRoute::ROW_BLOCK:
+      hipLaunchKernelGGL((row_reduce_block<T, OP>), dim3((unsigned)outer), dim3(1024), 0, s, x, y, r);
+      return;
+    case RedRoute::ROW_SPLIT:
+    case RedRoute::ROW_SPLIT_FOLD:  // outer < 1024 here: it fits grid.y
+      hipLaunchKernelGGL((row_split<T, OP>), dim3((unsigned)p.S, (unsigned)outer), dim3(256), 0, s, x, part, outer, r,
+                         p.rows_per_split);
+      final_pass<T, OP>(part, y, outer, p.S, r, s);
+      return;
+    default: break;
   }
-  TFA_CHECK(outer <= 65535, "reduce: outer dim ", outer, " too large for the column path");
-  A* part = S > 1 ? static_cast<A*>(ws) : nullptr;
-  TFA_CHECK(S == 1 || ws != nullptr, "reduce: missing workspace");
-  dim3 grid((unsigned)p.col_blocks, (unsigned)outer, (unsigned)S);
-  bool vec_ok = p.vec > 1 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  if (vec_ok) {
-    constexpr int VEC = 16 / sizeof(T);
-    hipLaunchKernelGGL((col_reduce_vec<T, OP, VEC>), grid, dim3(256), 0, s, x, y, part, outer, r, inner,
-                       rows_per_split);
-  } else {
-    dim3 g2((unsigned)((inner + 255) / 256), (unsigned)outer, (unsigned)S);
-    hipLaunchKernelGGL((col_reduce<T, OP>), g2, dim3(256), 0, s, x, y, part, outer, r, inner, rows_per_split);
+  // column path; grid.y holds at most kMaxGridY outer slices per launch
+  for (int64_t o0 = 0; o0 < outer; o0 += kMaxGridY) {
+    const int64_t no = std::min<int64_t>(kMaxGridY, outer - o0);
+    dim3 grid((unsigned)p.col_blocks, (unsigned)no, (unsigned)p.S);
+    const T* xo = x + o0 * r * inner;
+    T* yo = y + o0 * inner;
+    if (p.vec > 1)
+      hipLaunchKernelGGL((col_reduce_vec<T, OP, VEC>), grid, dim3(256), 0, s, xo, yo, part, outer, r, inner,
+                         p.rows_per_split);
+    else
+      hipLaunchKernelGGL((col_reduce<T, OP>), grid, dim3(256), 0, s, xo, yo, part, outer, r, inner, p.rows_per_split);
   }
-  if (S > 1) {
-    final_pass<T, OP>(part, y, outer * inner, S, r, s);
-  }
+  if (p.S > 1) final_pass<T, OP>(part, y, outer * inner, p.S, r, s);
 }
 
 template <typename T>
-void reduce_dispatch_op(RedOp op, const void* x, void* y, int64_t outer, int64_t r, int64_t inner,
+void reduce_dispatch_op(RedOp op, DType dt, const void* x, void* y, int64_t outer, int64_t r, int64_t inner,
                         void* ws, hipStream_t s) {
   switch (op) {
-    case RedOp::SUM: reduce_typed<T, (int)RedOp::SUM>(x, y, outer, r, inner, ws, s); break;
-    case RedOp::PROD: reduce_typed<T, (int)RedOp::PROD>(x, y, outer, r, inner, ws, s); break;
-    case RedOp::MIN: reduce_typed<T, (int)RedOp::MIN>(x, y, outer, r, inner, ws, s); break;
-    case RedOp::MAX: reduce_typed<T, (int)RedOp::MAX>(x, y, outer, r, inner, ws, s); break;
-    case RedOp::MEAN: reduce_typed<T, (int)RedOp::MEAN>(x, y, outer, r, inner, ws, s); break;
+    case RedOp::SUM: reduce_typed<T, (int)RedOp::SUM>(dt, x, y, outer, r, inner, ws, s); break;
+    case RedOp::PROD: reduce_typed<T, (int)RedOp::PROD>(dt, x, y, outer, r, inner, ws, s); break;
+    case RedOp::MIN: reduce_typed<T, (int)RedOp::MIN>(dt, x, y, outer, r, inner, ws, s); break;
+    case RedOp::MAX: reduce_typed<T, (int)RedOp::MAX>(dt, x, y, outer, r, inner, ws, s); break;
+    case RedOp::MEAN: reduce_typed<T, (int)RedOp::MEAN>(dt, x, y, outer, r, inner, ws, s); break;
     default: TFA_CHECK(false, "reduce: op needs bool input");
   }
 }
@@ -384,15 +441,13 @@ __global__ __launch_bounds__(256) void argreduce_row(const T* __restrict__ x, O*
     int64_t bi = 0;
     for (int64_t i = lane; i < r; i += 64) {
       T v = p[i];
-      bool better = MIN ? (v < best || (v == best && i < bi)) : (v > best || (v == best && i < bi));
-      if (better) { best = v; bi = i; }
+      if (arg_better<T, MIN>(v, i, best, bi)) { best = v; bi = i; }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       T ov = __shfl_xor(best, off, 64);
       int64_t oi = __shfl_xor(bi, off, 64);
-      bool better = MIN ? (ov < best || (ov == best && oi < bi)) : (ov > best || (ov == best && oi < bi));
-      if (better) { best = ov; bi = oi; }
+      if (arg_better<T, MIN>(ov, oi, best, bi)) { best = ov; bi = oi; }
     }
     if (lane == 0) y[row] = (O)bi;
   }
@@ -410,7 +465,7 @@ __global__ __launch_bounds__(256) void argreduce_col(const T* __restrict__ x, O*
     int64_t bi = 0;
     for (int64_t i = 1; i < r; ++i) {
       T v = p[i * inner];
-      if (MIN ? v < best : v > best) { best = v; bi = i; }
+      if (arg_better<T, MIN>(v, i, best, bi)) { best = v; bi = i; }  // i > bi: a tie keeps the lower index
     }
     y[t] = (O)bi;
   }
@@ -461,7 +516,9 @@ __global__ __launch_bounds__(256) void softmax_rows(const T* __restrict__ x, T* 
   }
 }
 
-// ---- top-k: wave per row, k selection rounds ordered (value desc, index asc)
+// ---- top-k: wave per row, k selection rounds ordered (value desc, index asc);
+// NaN counts as the largest value, so the order is total and every round with
+// j < cols finds a candidate (no index outside [0, cols) is ever written)
 template <typename T>
 __global__ __launch_bounds__(256) void topk_rows(const T* __restrict__ x, T* __restrict__ vals,
                                                  int32_t* __restrict__ idx, int64_t rows, int64_t cols,
@@ -479,8 +536,8 @@ __global__ __launch_bounds__(256) void topk_rows(const T* __restrict__ x, T* __r
       for (int64_t i = lane; i < cols; i += 64) {
         T v = p[i];
         // eligible: strictly after the previous pick in (value desc, index asc) order
-        bool elig = pi < 0 || v < pv || (v == pv && i > pi);
-        if (elig && (!have || v > bv || (v == bv && i < bi))) {
+        bool elig = pi < 0 || ord_gt(pv, v) || (ord_eq(v, pv) && i > pi);
+        if (elig && (!have || ord_gt(v, bv) || (ord_eq(v, bv) && i < bi))) {
           have = true;
           bv = v;
           bi = i;
@@ -491,7 +548,7 @@ __global__ __launch_bounds__(256) void topk_rows(const T* __restrict__ x, T* __r
         T ov = __shfl_xor(bv, off, 64);
         int64_t oi = __shfl_xor(bi, off, 64);
         int oh = __shfl_xor((int)have, off, 64);
-        if (oh && (!have || ov > bv || (ov == bv && oi < bi))) {
+        if (oh && (!have || ord_gt(ov, bv) || (ord_eq(ov, bv) && oi < bi))) {
           have = true;
           bv = ov;
           bi = oi;
@@ -505,6 +562,30 @@ __global__ __launch_bounds__(256) void topk_rows(const T* __restrict__ x, T* __r
       }
     }
   }
+}
+
+// TF's rule for an unsorted segment Min / Max, the same on every route: the
+// result starts from the type's highest / lowest finite value. An empty
+// segment gets that value, and so does a float segment that holds nothing but
+// +inf (Min) / -inf (Max); a NaN passes through.
+template <typename T, int OP, typename A>
+__device__ __forceinline__ A useg_clamp(A acc) {
+  if constexpr (OP == (int)RedOp::MAX) {
+    const A lo = A(std::numeric_limits<T>::lowest());
+    return acc < lo ? lo : acc;
+  } else if constexpr (OP == (int)RedOp::MIN) {
+    const A hi = A(std::numeric_limits<T>::max());
+    return acc > hi ? hi : acc;
+  } else {
+    return acc;
+  }
+}
+
+// zero input rows: every segment is empty and gets the op's identity
+template <typename T>
+__global__ __launch_bounds__(256) void useg_fill(T* __restrict__ y, int64_t m, T v) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) y[i] = v;
 }
 
 // ---- unsorted segment reduce, deterministic LDS-private path.
@@ -580,16 +661,7 @@ __global__ __launch_bounds__(256) void useg_final(const typename AccT<T>::type* 
     }
     for (int s = G / 2; s >= 1; s >>= 1) acc = combine<OP, A>(acc, __shfl_xor(acc, s, 64));
     if (i >= m || sub != 0) continue;
-    if constexpr (OP == (int)RedOp::MIN || OP == (int)RedOp::MAX) {
-      // TF: empty segments get the type's lowest (max) / highest (min) value
-      if (acc == ident<OP, A>()) {
-        if constexpr (std::is_floating_point<T>::value)
-          acc = OP == (int)RedOp::MAX ? A(-std::numeric_limits<T>::max()) : A(std::numeric_limits<T>::max());
-        else
-          acc = OP == (int)RedOp::MAX ? A(std::numeric_limits<T>::lowest()) : A(std::numeric_limits<T>::max());
-      }
-    }
-    y[i] = T(acc);
+    y[i] = T(useg_clamp<T, OP, A>(acc));
   }
 }
 
@@ -613,15 +685,7 @@ __global__ __launch_bounds__(256) void seg_csr(const T* __restrict__ x, const in
 // TF: an empty segment of a Min/Max gets the type's highest / lowest value
 template <typename T, int OP, typename A>
 __device__ __forceinline__ T seg_empty_or(A acc, int64_t count) {
-  if constexpr (OP == (int)RedOp::MIN || OP == (int)RedOp::MAX) {
-    if (count == 0) {
-      if constexpr (std::is_floating_point<T>::value)
-        return OP == (int)RedOp::MAX ? -std::numeric_limits<T>::max() : std::numeric_limits<T>::max();
-      else
-        return OP == (int)RedOp::MAX ? std::numeric_limits<T>::lowest() : std::numeric_limits<T>::max();
-    }
-  }
-  return finish<OP, T, A>(acc, count);
+  return finish<OP, T, A>(useg_clamp<T, OP, A>(acc), count);
 }
 
 template <typename T, int OP>
@@ -677,18 +741,15 @@ int64_t useg_blocks(int64_t n, int64_t nseg, int64_t inner) {
 
 // ====================================================================== host API
 size_t reduce_workspace_bytes(DType dt, int64_t outer, int64_t r, int64_t inner) {
-  int64_t S = 1;
   switch (dt) {
-    case DType::F32: { auto p = plan_reduce<float>(outer, r, inner); S = p.row_wave ? 1 : p.S; break; }
-    case DType::F64: { auto p = plan_reduce<double>(outer, r, inner); S = p.row_wave ? 1 : p.S; break; }
-    case DType::I32: { auto p = plan_reduce<int32_t>(outer, r, inner); S = p.row_wave ? 1 : p.S; break; }
-    case DType::I64: { auto p = plan_reduce<int64_t>(outer, r, inner); S = p.row_wave ? 1 : p.S; break; }
-    case DType::BOOL: { auto p = plan_reduce<uint8_t>(outer, r, inner); S = p.row_wave ? 1 : p.S; break; }
+    case DType::F32: case DType::F64: case DType::I32: case DType::I64: case DType::BOOL: break;
     default: return 0;
   }
-  if (S <= 1) return 0;
+  // S and the fold do not depend on the pointer's alignment
+  const ReducePlan p = reduce_route(dt, outer, r, inner, true);
+  if (p.S <= 1) return 0;
   // accumulators are 8 bytes: S partial slabs + the folded ones
-  return static_cast<size_t>(S + fold_slabs(S)) * outer * inner * 8;
+  return static_cast<size_t>(p.S + p.fold) * outer * inner * 8;
 }
 
 void reduce(RedOp op, DType dt, const void* x, void* y, int64_t outer, int64_t r, int64_t inner,
@@ -696,13 +757,13 @@ void reduce(RedOp op, DType dt, const void* x, void* y, int64_t outer, int64_t r
   if (outer * inner <= 0) return;
   TFA_CHECK(r > 0, "reduce: empty reduction handled by caller");
   switch (dt) {
-    case DType::F32: reduce_dispatch_op<float>(op, x, y, outer, r, inner, workspace, s); break;
-    case DType::F64: reduce_dispatch_op<double>(op, x, y, outer, r, inner, workspace, s); break;
-    case DType::I32: reduce_dispatch_op<int32_t>(op, x, y, outer, r, inner, workspace, s); break;
-    case DType::I64: reduce_dispatch_op<int64_t>(op, x, y, outer, r, inner, workspace, s); break;
+    case DType::F32: reduce_dispatch_op<float>(op, dt, x, y, outer, r, inner, workspace, s); break;
+    case DType::F64: reduce_dispatch_op<double>(op, dt, x, y, outer, r, inner, workspace, s); break;
+    case DType::I32: reduce_dispatch_op<int32_t>(op, dt, x, y, outer, r, inner, workspace, s); break;
+    case DType::I64: reduce_dispatch_op<int64_t>(op, dt, x, y, outer, r, inner, workspace, s); break;
     case DType::BOOL:
-      if (op == RedOp::ALL) reduce_typed<uint8_t, (int)RedOp::ALL>(x, y, outer, r, inner, workspace, s);
-      else if (op == RedOp::ANY) reduce_typed<uint8_t, (int)RedOp::ANY>(x, y, outer, r, inner, workspace, s);
+      if (op == RedOp::ALL) reduce_typed<uint8_t, (int)RedOp::ALL>(dt, x, y, outer, r, inner, workspace, s);
+      else if (op == RedOp::ANY) reduce_typed<uint8_t, (int)RedOp::ANY>(dt, x, y, outer, r, inner, workspace, s);
       else TFA_CHECK(false, "reduce: only All/Any on bool");
       break;
     default: TFA_CHECK(false, "reduce: dtype ", dtype_name(dt), " not supported");
@@ -764,16 +825,24 @@ static bool useg_fits_lds(int64_t inner, int64_t nseg) {
 
 static size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
-size_t unsorted_segment_workspace_bytes(RedOp, DType, int64_t n, int64_t inner, int64_t nseg) {
-  if (useg_fits_lds(inner, nseg)) return static_cast<size_t>(useg_blocks(n, nseg, inner)) * nseg * inner * 8;
-  return align256(n * 8) + align256((nseg + 1) * 8) + segment_csr_workspace_bytes(n, nseg);
+size_t unsorted_segment_workspace_bytes(RedOp op, DType dt, int64_t n, int64_t inner, int64_t nseg) {
+  if (unsorted_segment_route(op, dt, n, inner, nseg).route == UsegRoute::SORTED_PERM)
+    return align256(n * 8) + align256((nseg + 1) * 8) + segment_csr_workspace_bytes(n, nseg);
+  // the slabs of the LDS-private pass; the tiny integer route's partials fit in them
+  return static_cast<size_t>(useg_blocks(n, nseg, inner)) * nseg * inner * 8;
+}
+
+// columns of one row slot in seg_perm: inner rounded up to a power of two, at most 64
+static int seg_inner_pad(int64_t inner) {
+  int inner_pad = 1;
+  while (inner_pad < inner && inner_pad < 64) inner_pad <<= 1;
+  return inner_pad;
 }
 
 template <typename T>
 static void seg_perm_op(RedOp op, const void* x, const int64_t* perm, const int64_t* off, void* y, int64_t nseg,
                         int64_t inner, hipStream_t s) {
-  int inner_pad = 1;
-  while (inner_pad < inner && inner_pad < 64) inner_pad <<= 1;
+  const int inner_pad = seg_inner_pad(inner);
   dim3 grid((unsigned)((nseg + 3) / 4));
   switch (op) {
 #define TFA_SP(OPV) hipLaunchKernelGGL((seg_perm<T, (int)OPV>), grid, dim3(256), 0, s, (const T*)x, perm, off, (T*)y, nseg, inner, inner_pad); break;
@@ -836,13 +905,7 @@ __global__ __launch_bounds__(1024) void useg_small_int(const T* __restrict__ x, 
   }
   __syncthreads();
   for (int64_t g = threadIdx.x; g < nseg; g += 1024) {
-    long long a = acc[g];
-    if constexpr (OP == (int)RedOp::MIN || OP == (int)RedOp::MAX) {
-      // TF: empty segments get the type's highest (min) / lowest (max) value
-      if (a == ident<OP, long long>())
-        a = OP == (int)RedOp::MAX ? (long long)std::numeric_limits<T>::lowest() : (long long)std::numeric_limits<T>::max();
-    }
-    y[g] = T(a);
+    y[g] = T(useg_clamp<T, OP, long long>(acc[g]));
   }
 }
 
@@ -912,23 +975,58 @@ __global__ __launch_bounds__(64) void useg_tiny_final(const long long* __restric
 #pragma unroll
     for (int r = 0; r < R; ++r) a = combine<OP, long long>(a, t[r]);
   }
-  if constexpr (OP == (int)RedOp::MIN || OP == (int)RedOp::MAX) {
-    // TF: empty segments get the type's highest (min) / lowest (max) value
-    if (a == ident<OP, long long>())
-      a = OP == (int)RedOp::MAX ? (long long)std::numeric_limits<T>::lowest() : (long long)std::numeric_limits<T>::max();
+  y[g] = T(useg_clamp<T, OP, long long>(a));
+}
+
+// ---- routing of the unsorted segment reduce, written once (as reduce_route)
+UsegPlan unsorted_segment_route(RedOp op, DType dt, int64_t n, int64_t inner, int64_t nseg) {
+  UsegPlan p;
+  if (!useg_fits_lds(inner, nseg)) {
+    p.route = UsegRoute::SORTED_PERM;
+    p.inner_pad = seg_inner_pad(inner);
+    p.wide = inner > 64;  // the wave loops over 64-column chunks
+    return p;
   }
-  y[g] = T(a);
+  if (dtype_is_int(dt) && op != RedOp::PROD && inner == 1 && n <= kUsegSmallRows) {
+    if (nseg <= kUsegRegSegs) {
+      p.route = UsegRoute::TINY_INT;
+      p.B = (n + kUsegTinyRows - 1) / kUsegTinyRows;
+      return p;
+    }
+    // the LDS test above already holds nseg to 128 at inner == 1, so the
+    // table of kUsegSmallSegs entries is never full
+    if (nseg <= kUsegSmallSegs) {
+      p.route = UsegRoute::SMALL_INT;
+      return p;
+    }
+  }
+  p.route = UsegRoute::PRIVATE;
+  p.tile = useg_tile(inner);
+  p.rows_per_block = useg_rows_per_block(n, nseg, inner);
+  p.B = useg_blocks(n, nseg, inner);
+  p.G = 1;
+  while (p.G < 64 && p.G < p.B) p.G <<= 1;
+  return p;
+}
+
+std::string unsorted_segment_route_name(const UsegPlan& p) {
+  switch (p.route) {
+    case UsegRoute::TINY_INT: return "tiny_int";
+    case UsegRoute::SMALL_INT: return "small_int";
+    case UsegRoute::PRIVATE: return "private_g" + std::to_string(p.G);
+    default: return p.wide ? "sorted_perm_wide" : "sorted_perm_p" + std::to_string(p.inner_pad);
+  }
 }
 
 template <typename T, typename I, int OP>
-static void useg_typed(const void* x, const void* ids, void* y, int64_t n, int64_t inner, int64_t nseg,
-                       void* ws, hipStream_t s) {
+static void useg_typed(const UsegPlan& p, const void* x, const void* ids, void* y, int64_t n, int64_t inner,
+                       int64_t nseg, void* ws, hipStream_t s) {
   using A = typename AccT<T>::type;
   if constexpr (std::is_integral<T>::value && OP != (int)RedOp::PROD) {
-    if (inner == 1 && n <= kUsegSmallRows && nseg <= kUsegRegSegs) {
+    if (p.route == UsegRoute::TINY_INT) {
       // partials: B x nseg 8-byte values, within the workspace of the
       // LDS-private pass (B <= n / 1024 <= useg_blocks(n, nseg, 1))
-      const int64_t B = (n + kUsegTinyRows - 1) / kUsegTinyRows;
+      const int64_t B = p.B;
       long long* part = static_cast<long long*>(ws);
       hipLaunchKernelGGL((useg_tiny_int<T, I, OP>), dim3((unsigned)B), dim3(kUsegTinyThreads), 0, s, (const T*)x,
                          (const I*)ids, part, n, (int)nseg);
@@ -936,52 +1034,74 @@ static void useg_typed(const void* x, const void* ids, void* y, int64_t n, int64
                          (int)nseg);
       return;
     }
-    if (inner == 1 && n <= kUsegSmallRows && nseg <= kUsegSmallSegs) {
+    if (p.route == UsegRoute::SMALL_INT) {
       hipLaunchKernelGGL((useg_small_int<T, I, OP>), dim3(1), dim3(1024), 0, s, (const T*)x, (const I*)ids, (T*)y, n,
                          nseg);
       return;
     }
   }
-  int64_t tile = useg_tile(inner);
+  TFA_CHECK(p.route == UsegRoute::PRIVATE, "unsorted segment reduce: no kernel for this route");
+  const int64_t tile = p.tile, rpb = p.rows_per_block, B = p.B;
   size_t lds = static_cast<size_t>(nseg * tile * sizeof(A));
   TFA_CHECK(lds <= kUsegLds, "unsorted segment reduce: ", nseg, " segments x ", tile,
             " columns exceed the LDS budget");
-  const int64_t rpb = useg_rows_per_block(n, nseg, inner);
-  const int64_t B = useg_blocks(n, nseg, inner);
   dim3 grid((unsigned)B, (unsigned)((inner + tile - 1) / tile));
   hipLaunchKernelGGL((useg_private<T, I, OP>), grid, dim3((unsigned)tile), lds, s, (const T*)x, (const I*)ids,
                      (A*)ws, n, inner, nseg, rpb);
   const int64_t m = nseg * inner;
-  int G = 1;
-  while (G < 64 && G < B) G <<= 1;
+  const int G = p.G;
   const int64_t groups = (m + 64 / G - 1) / (64 / G);  // waves
   const unsigned fgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, 65536));
   hipLaunchKernelGGL((useg_final<T, OP>), dim3(fgrid), dim3(256), 0, s, (const A*)ws, (T*)y, m, B, G);
 }
 
 template <typename T, typename I>
-static void useg_op(RedOp op, const void* x, const void* ids, void* y, int64_t n, int64_t inner,
+static void useg_op(const UsegPlan& p, RedOp op, const void* x, const void* ids, void* y, int64_t n, int64_t inner,
                     int64_t nseg, void* ws, hipStream_t s) {
   switch (op) {
-    case RedOp::SUM: useg_typed<T, I, (int)RedOp::SUM>(x, ids, y, n, inner, nseg, ws, s); break;
-    case RedOp::PROD: useg_typed<T, I, (int)RedOp::PROD>(x, ids, y, n, inner, nseg, ws, s); break;
-    case RedOp::MIN: useg_typed<T, I, (int)RedOp::MIN>(x, ids, y, n, inner, nseg, ws, s); break;
-    case RedOp::MAX: useg_typed<T, I, (int)RedOp::MAX>(x, ids, y, n, inner, nseg, ws, s); break;
+    case RedOp::SUM: useg_typed<T, I, (int)RedOp::SUM>(p, x, ids, y, n, inner, nseg, ws, s); break;
+    case RedOp::PROD: useg_typed<T, I, (int)RedOp::PROD>(p, x, ids, y, n, inner, nseg, ws, s); break;
+    case RedOp::MIN: useg_typed<T, I, (int)RedOp::MIN>(p, x, ids, y, n, inner, nseg, ws, s); break;
+    case RedOp::MAX: useg_typed<T, I, (int)RedOp::MAX>(p, x, ids, y, n, inner, nseg, ws, s); break;
     default: TFA_CHECK(false, "unsorted segment reduce: unsupported op");
   }
+}
+
+// no input rows: every segment is empty. Sum 0, Prod 1, Min the type's
+// highest and Max its lowest value, as every route gives an empty segment
+template <typename T>
+static void useg_fill_typed(RedOp op, void* y, int64_t m, hipStream_t s) {
+  T v = T(0);
+  if (op == RedOp::PROD) v = T(1);
+  if (op == RedOp::MIN) v = std::numeric_limits<T>::max();
+  if (op == RedOp::MAX) v = std::numeric_limits<T>::lowest();
+  hipLaunchKernelGGL((useg_fill<T>), dim3(ew_grid(m)), dim3(256), 0, s, (T*)y, m, v);
+}
+
+static void useg_fill_identity(RedOp op, DType dt, void* y, int64_t m, hipStream_t s) {
+  TFA_CHECK(op == RedOp::SUM || op == RedOp::PROD || op == RedOp::MIN || op == RedOp::MAX,
+            "unsorted segment reduce: unsupported op");
+  switch (dt) {
+    case DType::F32: useg_fill_typed<float>(op, y, m, s); break;
+    case DType::F64: useg_fill_typed<double>(op, y, m, s); break;
+    case DType::I32: useg_fill_typed<int32_t>(op, y, m, s); break;
+    case DType::I64: useg_fill_typed<int64_t>(op, y, m, s); break;
+    default: TFA_CHECK(false, "unsorted segment reduce: dtype not supported");
+  }
+  TFA_LAUNCH_CHECK("unsorted_segment_reduce");
 }
 
 void unsorted_segment_reduce(RedOp op, DType dt, DType idt, const void* x, const void* ids, void* y,
                              int64_t n, int64_t inner, int64_t nseg, void* workspace, hipStream_t s) {
   if (nseg * inner <= 0) return;
   if (n == 0) {
-    double v = (op == RedOp::PROD) ? 1.0 : 0.0;
-    fill(dt, y, nseg * inner, v, s);
+    useg_fill_identity(op, dt, y, nseg * inner, s);
     return;
   }
   TFA_CHECK(workspace != nullptr, "unsorted segment reduce: missing workspace");
   TFA_CHECK(idt == DType::I32 || idt == DType::I64, "segment ids must be int32/int64");
-  if (!useg_fits_lds(inner, nseg)) {
+  const UsegPlan plan = unsorted_segment_route(op, dt, n, inner, nseg);
+  if (plan.route == UsegRoute::SORTED_PERM) {
     char* p = static_cast<char*>(workspace);
     int64_t* perm = reinterpret_cast<int64_t*>(p);
     int64_t* off = reinterpret_cast<int64_t*>(p + align256(n * 8));
@@ -992,10 +1112,10 @@ void unsorted_segment_reduce(RedOp op, DType dt, DType idt, const void* x, const
   }
   bool i64 = idt == DType::I64;
   switch (dt) {
-    case DType::F32: i64 ? useg_op<float, int64_t>(op, x, ids, y, n, inner, nseg, workspace, s) : useg_op<float, int32_t>(op, x, ids, y, n, inner, nseg, workspace, s); break;
-    case DType::F64: i64 ? useg_op<double, int64_t>(op, x, ids, y, n, inner, nseg, workspace, s) : useg_op<double, int32_t>(op, x, ids, y, n, inner, nseg, workspace, s); break;
-    case DType::I32: i64 ? useg_op<int32_t, int64_t>(op, x, ids, y, n, inner, nseg, workspace, s) : useg_op<int32_t, int32_t>(op, x, ids, y, n, inner, nseg, workspace, s); break;
-    case DType::I64: i64 ? useg_op<int64_t, int64_t>(op, x, ids, y, n, inner, nseg, workspace, s) : useg_op<int64_t, int32_t>(op, x, ids, y, n, inner, nseg, workspace, s); break;
+    case DType::F32: i64 ? useg_op<float, int64_t>(plan, op, x, ids, y, n, inner, nseg, workspace, s) : useg_op<float, int32_t>(plan, op, x, ids, y, n, inner, nseg, workspace, s); break;
+    case DType::F64: i64 ? useg_op<double, int64_t>(plan, op, x, ids, y, n, inner, nseg, workspace, s) : useg_op<double, int32_t>(plan, op, x, ids, y, n, inner, nseg, workspace, s); break;
+    case DType::I32: i64 ? useg_op<int32_t, int64_t>(plan, op, x, ids, y, n, inner, nseg, workspace, s) : useg_op<int32_t, int32_t>(plan, op, x, ids, y, n, inner, nseg, workspace, s); break;
+    case DType::I64: i64 ? useg_op<int64_t, int64_t>(plan, op, x, ids, y, n, inner, nseg, workspace, s) : useg_op<int64_t, int32_t>(plan, op, x, ids, y, n, inner, nseg, workspace, s); break;
     default: TFA_CHECK(false, "unsorted segment reduce: dtype not supported");
   }
   TFA_LAUNCH_CHECK("unsorted_segment_reduce");
