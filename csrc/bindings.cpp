@@ -576,10 +576,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     TFA_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.dim() == 1, "group_representatives: device int64 ids");
     c10::hip::HIPGuard guard(ids.device().index());
     at::Tensor rep = pool_empty({nseg}, ids.options());
-    k::group_representatives(ids.contiguous().data_ptr<int64_t>(), ids.size(0), rep.data_ptr<int64_t>(),
+    k::group_representatives(ids.contiguous().data_ptr<int64_t>(), ids.size(0), nseg, rep.data_ptr<int64_t>(),
                              c10::hip::getCurrentHIPStream(ids.device().index()).stream());
     return rep;
-  }, "one row index per group (device)");
+  }, "the last row index of every group (device), as the host path's rep[ids] = arange(n)");
   m.def("partition_rows", [](const at::Tensor& dest0, int64_t world) {
     TFA_CHECK(dest0.is_cuda() && dest0.scalar_type() == at::kLong && dest0.dim() == 1, "partition_rows: device int64 dest");
     c10::hip::HIPGuard guard(dest0.device().index());
@@ -1726,6 +1726,90 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     for (int i = 0; i < (int)k::RedRoute::COUNT; ++i) v.push_back(k::reduce_route_name((k::RedRoute)i));
     return v;
   }, "every name reduce_route can return");
+  // The host-side routing of kernels/gemm_f64.hip: f64 GEMM, integer GEMM, pooling.
+  m.def("gemm_f64_route", [](int64_t M, int64_t N, int64_t K, int64_t batch, bool ta, bool tb, int64_t lda, int64_t ldb,
+                             bool a_aligned16, bool b_aligned16) {
+    TFA_CHECK(M > 0 && N > 0 && K >= 0 && batch > 0, "gemm_f64_route: M, N and batch must be positive");
+    if (lda <= 0) lda = ta ? M : K;
+    if (ldb <= 0) ldb = tb ? K : N;
+    const k::GemmF64Plan p = k::gemm_f64_route(M, N, K, batch, ta, tb, lda, ldb, a_aligned16, b_aligned16);
+    py::dict d;
+    d["tile"] = std::string(k::gemm_f64_tile_name(p.tile));
+    d["kernel"] = std::string(k::gemm_f64_tile_name(p.tile)) + (ta ? "_T" : "_N") + (tb ? "T" : "N");
+    d["BM"] = p.BM;
+    d["BN"] = p.BN;
+    d["tiles_m"] = p.tiles_m;
+    d["tiles_n"] = p.tiles_n;
+    d["grid"] = py::make_tuple(p.tiles_m * p.tiles_n, 1, std::min(batch, k::kGemmMaxBatchPerLaunch));
+    d["launches"] = p.launches;
+    d["max_batch_per_launch"] = k::kGemmMaxBatchPerLaunch;
+    d["k_mult16"] = p.k_mult16;
+    d["a_pairs"] = p.a_pairs;
+    d["b_pairs"] = p.b_pairs;
+    return d;
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("batch") = 1, py::arg("ta") = false, py::arg("tb") = false,
+     py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("a_aligned16") = true, py::arg("b_aligned16") = true,
+     "the launch k::gemm takes for a float64 GEMM (lda / ldb 0: the contiguous operand)");
+  m.def("gemm_f64_kernel_names", [] {
+    std::vector<std::string> v;
+    for (int t = 0; t < (int)k::F64Tile::COUNT; ++t)
+      for (const char* tr : {"_NN", "_NT", "_TN", "_TT"}) v.push_back(std::string(k::gemm_f64_tile_name((k::F64Tile)t)) + tr);
+    return v;
+  }, "every `kernel` gemm_f64_route can return: tile x transpose_a x transpose_b");
+  m.def("gemm_int_route", [](int64_t M, int64_t N, int64_t K, int64_t batch) {
+    TFA_CHECK(M > 0 && N > 0 && K >= 0 && batch > 0, "gemm_int_route: M, N and batch must be positive");
+    const k::GemmIntPlan p = k::gemm_int_route(M, N, K, batch);
+    py::dict d;
+    d["tiles_m"] = p.tiles_m;
+    d["tiles_n"] = p.tiles_n;
+    d["grid"] = py::make_tuple(p.tiles_m * p.tiles_n, 1, std::min(batch, k::kGemmMaxBatchPerLaunch));
+    d["launches"] = p.launches;
+    d["max_batch_per_launch"] = k::kGemmMaxBatchPerLaunch;
+    d["max_grid_x"] = (int64_t(1) << 31) - 1;
+    return d;
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("batch") = 1,
+     "the launch k::gemm takes for an int32 / int64 GEMM and the limits that apply");
+  auto pool_plan = [](int64_t N, int64_t H, int64_t W, int64_t C, int64_t OH, int64_t OW, int64_t KH, int64_t KW,
+                      int64_t ldc, bool x_aligned16, bool y_aligned16) {
+    TFA_CHECK(N > 0 && H > 0 && W > 0 && C > 0 && OH > 0 && OW > 0 && KH > 0 && KW > 0 && ldc >= 0,
+              "pool_route: sizes must be positive");
+    k::PoolArgs a{};
+    a.N = N; a.H = H; a.W = W; a.C = C; a.OH = OH; a.OW = OW; a.KH = KH; a.KW = KW; a.ldc = ldc;
+    return k::pool_route(a, x_aligned16, y_aligned16);
+  };
+  m.def("pool_route", [pool_plan](int64_t N, int64_t H, int64_t W, int64_t C, int64_t OH, int64_t OW, int64_t KH,
+                                  int64_t KW, int64_t ldc, bool x_aligned16, bool y_aligned16) {
+    return std::string(k::pool_route_name(pool_plan(N, H, W, C, OH, OW, KH, KW, ldc, x_aligned16, y_aligned16).route));
+  }, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("OH"), py::arg("OW"), py::arg("KH"), py::arg("KW"),
+     py::arg("ldc") = 0, py::arg("x_aligned16") = true, py::arg("y_aligned16") = true,
+     "name of the kernel k::pool2d_nhwc takes (under TFA_POOL_GENERIC / TFA_POOL_XCD and set_pool_route)");
+  m.def("pool_route_info", [pool_plan](int64_t N, int64_t H, int64_t W, int64_t C, int64_t OH, int64_t OW, int64_t KH,
+                                       int64_t KW, int64_t ldc, bool x_aligned16, bool y_aligned16) {
+    const k::PoolPlan p = pool_plan(N, H, W, C, OH, OW, KH, KW, ldc, x_aligned16, y_aligned16);
+    py::dict d;
+    d["route"] = std::string(k::pool_route_name(p.route));
+    d["V"] = p.V;
+    d["items"] = p.items;
+    d["blocks"] = p.blocks;
+    return d;
+  }, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("OH"), py::arg("OW"), py::arg("KH"), py::arg("KW"),
+     py::arg("ldc") = 0, py::arg("x_aligned16") = true, py::arg("y_aligned16") = true);
+  m.def("pool_route_names", [] {
+    std::vector<std::string> v;
+    for (int i = 0; i < (int)k::PoolRoute::COUNT; ++i) v.push_back(k::pool_route_name((k::PoolRoute)i));
+    return v;
+  }, "every name pool_route can return, from the most to the least specialised");
+  m.def("set_pool_route", [](py::object route) {
+    if (route.is_none()) return k::set_pool_route(-1);
+    if (py::isinstance<py::str>(route)) {
+      const std::string name = route.cast<std::string>();
+      for (int i = 0; i < (int)k::PoolRoute::COUNT; ++i)
+        if (name == k::pool_route_name((k::PoolRoute)i)) return k::set_pool_route(i);
+      TFA_CHECK(false, "set_pool_route: unknown route ", name);
+    }
+    k::set_pool_route(route.cast<int>());
+  }, py::arg("route"),
+     "force a pool kernel process-wide (None or -1: automatic); only a less specialised route than the automatic one");
   m.def("unsorted_segment_route", [route_dtype, route_redop](const std::string& op, const std::string& dtype, int64_t n,
                                                              int64_t inner, int64_t nseg) {
     TFA_CHECK(n > 0 && inner > 0 && nseg > 0, "unsorted_segment_route: n, inner and nseg must be positive");

@@ -438,8 +438,19 @@ void run_gemm(ExecCtx& c, const at::Tensor& a0, const at::Tensor& b0, bool ta, b
   g.batch = batch;
   if (M == 0 || N == 0) return;
   if (K == 0) {
-    k::fill(dt_of(out), out.data_ptr(), out.numel(), 0.0, stream_of(c));
-    return;
+    if (!bias && act == k::ACT_NONE && !epi && out.is_contiguous()) {
+      k::fill(dt_of(out), out.data_ptr(), out.numel(), 0.0, stream_of(c));
+      return;
+    }
+    // an empty sum is 0, and the fused bias / activation / chain still apply
+    // to it (as on the host): the same GEMM over one zero column times one
+    // zero row, shared by every batch
+    a = c.alloc({M + N}, a.options());
+    k::fill(dt_of(a), a.data_ptr(), M + N, 0.0, stream_of(c));
+    g.K = 1;
+    g.A = a.data_ptr(); g.lda = 1; g.strideA = 0;
+    g.B = static_cast<const char*>(a.data_ptr()) + M * a.element_size(); g.ldb = N; g.strideB = 0;
+    g.ta = false; g.tb = false;
   }
   at::Tensor work;
   if (size_t ws = k::gemm_workspace_bytes(dt_of(a), g)) {

@@ -264,8 +264,8 @@ __device__ __forceinline__ T un_apply(int op, T x) {
     case (int)UnOp::RECIP:
       if constexpr (F) return T(1) / x;
       else return x == 0 ? T(0) : T(1 / x);
-    case (int)UnOp::RELU: return x > T(0) ? x : T(0);
-    case (int)UnOp::RELU6: return x > T(0) ? (x < T(6) ? x : T(6)) : T(0);
+    case (int)UnOp::RELU: return x < T(0) ? T(0) : x;  // NaN stays NaN, as clamp_min on the host
+    case (int)UnOp::RELU6: return x < T(0) ? T(0) : (x > T(6) ? T(6) : x);
     case (int)UnOp::ELU: return x > T(0) ? x : T(expm1(xc));
     case (int)UnOp::SELU: {
       const C alpha = C(1.6732632423543772848170429916717), scale = C(1.0507009873554804934193349852946);

@@ -4,7 +4,10 @@
 // wave 32x32 = 2x2 MFMA tiles of 16x16 (f64 has its own C/D layout:
 // col = lane&15, row = (lane>>4) + 4*reg). k-major LDS images, two stages,
 // register-staged prefetch of the next K tile, bias/ReLU epilogue.
+#include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <cstdlib>
 
 #include <type_traits>
 
@@ -51,7 +54,7 @@ __device__ __forceinline__ void sched_interleave64() {
 // (BM/2)x(BN/2) as TMxTN 16x16 MFMA tiles. Interior blocks load 2 doubles per
 // 16-byte access without bounds checks; edge blocks take the checked path.
 template <int BM, int BN, int WM, int WN, bool TA, bool TB>
-__global__ __launch_bounds__(256, 2) void gemm_f64_mfma(GemmArgs g, int tiles_m, int tiles_n) {
+__global__ __launch_bounds__(256, 2) void gemm_f64_mfma(GemmArgs g, int tiles_m, int tiles_n, int64_t batch0) {
   constexpr int LDA = BM + D_PAD, LDB = BN + D_PAD;
   constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
   static_assert(WM * WN == 4 && TM >= 1 && TN >= 1, "4 waves, >= one 16x16 tile each");
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_mfma(GemmArgs g, int tiles_m,
   const int wg = xcd_remap64(blockIdx.x, nwg);
   const int64_t m0 = (int64_t)(wg / tiles_n) * BM;
   const int64_t n0 = (int64_t)(wg % tiles_n) * BN;
-  const int64_t bz = blockIdx.z;
+  const int64_t bz = batch0 + blockIdx.z;  // batches run in grid.z slices
   const double* A = static_cast<const double*>(g.A) + bz * g.strideA;
   const double* B = static_cast<const double*>(g.B) + bz * g.strideB;
   double* C = static_cast<double*>(g.C) + bz * g.strideC;
@@ -253,20 +256,21 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_mfma(GemmArgs g, int tiles_m,
 
 // ============================================================== integer GEMM (VALU)
 template <typename T>
-__global__ __launch_bounds__(256) void gemm_int(GemmArgs g) {
+__global__ __launch_bounds__(256) void gemm_int(GemmArgs g, int tiles_n, int64_t batch0) {
   __shared__ T As[16][17];
   __shared__ T Bs[16][17];
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  const int64_t row = (int64_t)blockIdx.y * 16 + ty, col = (int64_t)blockIdx.x * 16 + tx;
-  const int64_t bz = blockIdx.z;
+  // 16x16 tiles row-major over grid.x (grid.y would cap M at 16 * 65535 rows)
+  const int64_t tile_m = blockIdx.x / (unsigned)tiles_n, tile_n = blockIdx.x % (unsigned)tiles_n;
+  const int64_t row = tile_m * 16 + ty, col = tile_n * 16 + tx;
+  const int64_t bz = batch0 + blockIdx.z;
   const T* A = static_cast<const T*>(g.A) + bz * g.strideA;
   const T* B = static_cast<const T*>(g.B) + bz * g.strideB;
   T* C = static_cast<T*>(g.C) + bz * g.strideC;
   int64_t acc = 0;
   for (int64_t k0 = 0; k0 < g.K; k0 += 16) {
     const int64_t ka = k0 + tx, kb = k0 + ty;
-    const int64_t arow = (int64_t)blockIdx.y * 16 + ty;
-    const int64_t bcol = (int64_t)blockIdx.x * 16 + tx;
+    const int64_t arow = row, bcol = col;
     As[ty][tx] = (arow < g.M && ka < g.K) ? (g.ta ? A[ka * g.lda + arow] : A[arow * g.lda + ka]) : T(0);
     Bs[ty][tx] = (bcol < g.N && kb < g.K) ? (g.tb ? B[bcol * g.ldb + kb] : B[kb * g.ldb + bcol]) : T(0);
     __syncthreads();
@@ -282,6 +286,11 @@ __global__ __launch_bounds__(256) void gemm_int(GemmArgs g) {
 }
 
 // ============================================================== pooling (NHWC)
+// max that keeps a NaN (fmaxf drops it), as at::max_pool2d of the host
+// executor and the Max reduction do: a NaN tap inside the image makes the
+// output NaN, a NaN accumulator stays
+__device__ __forceinline__ float nanmax(float acc, float v) { return (v > acc || v != v) ? v : acc; }
+
 // One thread per V consecutive channels of one output pixel (V = 4: float4
 // loads/stores when C % 4 == 0). Index math is 32-bit when the tensors fit
 // (64-bit div/mod costs ~40 VALU ops on CDNA).
@@ -324,7 +333,7 @@ __global__ __launch_bounds__(256) void pool2d_kernel(PoolArgs a, I n_items, Fast
         vec_t v = *reinterpret_cast<const vec_t*>(base + ((int64_t)ih * W + iw) * a.C);
         const float* f = reinterpret_cast<const float*>(&v);
 #pragma unroll
-        for (int j = 0; j < V; ++j) acc[j] = MAX ? fmaxf(acc[j], f[j]) : acc[j] + f[j];
+        for (int j = 0; j < V; ++j) acc[j] = MAX ? nanmax(acc[j], f[j]) : acc[j] + f[j];
       }
     }
     const int cnt = (he - hb) * (we - wb);
@@ -349,7 +358,8 @@ __global__ __launch_bounds__(256) void pool2d_kernel(PoolArgs a, I n_items, Fast
 // the nine taps are unrolled with clamped in-bounds addresses, so each lane
 // has all nine 16-byte loads in flight before the first max/add (the generic
 // kernel's data-dependent window loops issue them one at a time). Taps outside
-// the image are masked out of the result; avg divides by the valid-tap count
+// the image are masked out of the result (whatever the clamped address holds,
+// a NaN included); avg divides by the valid-tap count
 // (TF semantics). Same epilogue and concat-slice output as pool2d_kernel.
 //
 // XCD: one block per 256 items, and block b runs the items of block
@@ -393,7 +403,7 @@ __global__ __launch_bounds__(256) void pool3x3_v4_kernel(PoolArgs a, uint32_t n_
     for (int j = 0; j < 9; ++j) {
       const float4 u = ok[j] ? v[j] : make_float4(init, init, init, init);
       if (MAX) {
-        acc.x = fmaxf(acc.x, u.x); acc.y = fmaxf(acc.y, u.y); acc.z = fmaxf(acc.z, u.z); acc.w = fmaxf(acc.w, u.w);
+        acc.x = nanmax(acc.x, u.x); acc.y = nanmax(acc.y, u.y); acc.z = nanmax(acc.z, u.z); acc.w = nanmax(acc.w, u.w);
       } else {
         acc.x += u.x; acc.y += u.y; acc.z += u.z; acc.w += u.w;
       }
@@ -419,72 +429,183 @@ __global__ __launch_bounds__(256) void pool3x3_v4_kernel(PoolArgs a, uint32_t n_
 
 template <bool MAX>
 void pool2d_launch(const PoolArgs& a, hipStream_t s) {
-  const bool v4 = a.C % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(a.y) & 15) == 0 && a.ldc % 4 == 0;
-  const int V = v4 ? 4 : 1;
-  const int64_t items = a.N * a.OH * a.OW * (a.C / V);
-  const bool small = a.N * a.H * a.W * a.C < (int64_t(1) << 31) && a.N * a.OH * a.OW * a.C < (int64_t(1) << 31);
-  const dim3 grid(ew_grid(items)), block(256);
-  const FastDivU32 fCV = make_fastdiv((uint32_t)(a.C / V)), fOW = make_fastdiv((uint32_t)a.OW),
+  const PoolPlan p = pool_route(a, (reinterpret_cast<uintptr_t>(a.x) & 15) == 0, (reinterpret_cast<uintptr_t>(a.y) & 15) == 0);
+  const dim3 grid((unsigned)p.blocks), block(256);
+  const int64_t items = p.items;
+  const FastDivU32 fCV = make_fastdiv((uint32_t)(a.C / p.V)), fOW = make_fastdiv((uint32_t)a.OW),
                    fOH = make_fastdiv((uint32_t)a.OH);
-  static const bool generic = [] {
-    const char* e = std::getenv("TFA_POOL_GENERIC");
-    return e && e[0] == '1';
-  }();
-  const int64_t out_span = a.ldc ? a.N * a.OH * a.OW * a.ldc : a.N * a.OH * a.OW * a.C;
-  static const bool no_xcd = [] {
-    const char* e = std::getenv("TFA_POOL_XCD");
-    return e && e[0] == '0';
-  }();
-  if (v4 && small && a.KH == 3 && a.KW == 3 && out_span < (int64_t(1) << 31) && !generic) {
-    const int64_t nblk = (items + 255) / 256;
-    if (!no_xcd && nblk < (int64_t(1) << 30))
-      hipLaunchKernelGGL((pool3x3_v4_kernel<MAX, true>), dim3((unsigned)nblk), block, 0, s, a, (uint32_t)items, fCV,
-                         fOW, fOH);
-    else
+  switch (p.route) {
+    case PoolRoute::P3X3_V4_XCD:
+      hipLaunchKernelGGL((pool3x3_v4_kernel<MAX, true>), grid, block, 0, s, a, (uint32_t)items, fCV, fOW, fOH);
+      break;
+    case PoolRoute::P3X3_V4:
       hipLaunchKernelGGL((pool3x3_v4_kernel<MAX, false>), grid, block, 0, s, a, (uint32_t)items, fCV, fOW, fOH);
-    return;
+      break;
+    case PoolRoute::GENERIC_V4_U32:
+      hipLaunchKernelGGL((pool2d_kernel<MAX, 4, uint32_t>), grid, block, 0, s, a, (uint32_t)items, fCV, fOW, fOH);
+      break;
+    case PoolRoute::GENERIC_V4_I64:
+      hipLaunchKernelGGL((pool2d_kernel<MAX, 4, int64_t>), grid, block, 0, s, a, items, fCV, fOW, fOH);
+      break;
+    case PoolRoute::GENERIC_V1_U32:
+      hipLaunchKernelGGL((pool2d_kernel<MAX, 1, uint32_t>), grid, block, 0, s, a, (uint32_t)items, fCV, fOW, fOH);
+      break;
+    case PoolRoute::GENERIC_V1_I64:
+      hipLaunchKernelGGL((pool2d_kernel<MAX, 1, int64_t>), grid, block, 0, s, a, items, fCV, fOW, fOH);
+      break;
+    default: TFA_CHECK(false, "pool2d: no kernel for route ", (int)p.route);
   }
-  if (v4 && small)
-    hipLaunchKernelGGL((pool2d_kernel<MAX, 4, uint32_t>), grid, block, 0, s, a, (uint32_t)items, fCV, fOW, fOH);
-  else if (v4)
-    hipLaunchKernelGGL((pool2d_kernel<MAX, 4, int64_t>), grid, block, 0, s, a, items, fCV, fOW, fOH);
-  else if (small)
-    hipLaunchKernelGGL((pool2d_kernel<MAX, 1, uint32_t>), grid, block, 0, s, a, (uint32_t)items, fCV, fOW, fOH);
-  else
-    hipLaunchKernelGGL((pool2d_kernel<MAX, 1, int64_t>), grid, block, 0, s, a, items, fCV, fOW, fOH);
+}
+
+// forced pool route (-1 = automatic): set_pool_route()
+std::atomic<int>& forced_pool_route() {
+  static std::atomic<int> r{-1};
+  return r;
+}
+
+// what a route asks of the shape: {3x3 kernel, XCD grid, 32-bit indices, float4 channels}
+struct PoolNeeds {
+  bool k3, xcd, u32, v4;
+};
+PoolNeeds pool_needs(PoolRoute r) {
+  switch (r) {
+    case PoolRoute::P3X3_V4_XCD: return {true, true, true, true};
+    case PoolRoute::P3X3_V4: return {true, false, true, true};
+    case PoolRoute::GENERIC_V4_U32: return {false, false, true, true};
+    case PoolRoute::GENERIC_V4_I64: return {false, false, false, true};
+    case PoolRoute::GENERIC_V1_U32: return {false, false, true, false};
+    default: return {false, false, false, false};
+  }
 }
 
 }  // namespace
 
-template <int BM, int BN, int WM, int WN>
-static void gemm_f64_tile_launch(const GemmArgs& g, hipStream_t s) {
-  const int64_t tm = (g.M + BM - 1) / BM, tn = (g.N + BN - 1) / BN;
-  TFA_CHECK(tm * tn < (int64_t(1) << 31), "gemm: grid too large");
-  TFA_CHECK(g.batch <= 65535, "gemm: batch too large");
-  dim3 grid((unsigned)(tm * tn), 1, (unsigned)g.batch);
-  if (!g.ta && !g.tb) hipLaunchKernelGGL((gemm_f64_mfma<BM, BN, WM, WN, false, false>), grid, dim3(256), 0, s, g, (int)tm, (int)tn);
-  else if (!g.ta && g.tb) hipLaunchKernelGGL((gemm_f64_mfma<BM, BN, WM, WN, false, true>), grid, dim3(256), 0, s, g, (int)tm, (int)tn);
-  else if (g.ta && !g.tb) hipLaunchKernelGGL((gemm_f64_mfma<BM, BN, WM, WN, true, false>), grid, dim3(256), 0, s, g, (int)tm, (int)tn);
-  else hipLaunchKernelGGL((gemm_f64_mfma<BM, BN, WM, WN, true, true>), grid, dim3(256), 0, s, g, (int)tm, (int)tn);
+// ---- routing, written once: the launch code above and the tests read it
+const char* pool_route_name(PoolRoute r) {
+  static const char* const names[] = {"pool3x3_v4_xcd", "pool3x3_v4", "generic_v4_u32", "generic_v4_i64",
+                                      "generic_v1_u32", "generic_v1_i64"};
+  static_assert(sizeof(names) / sizeof(names[0]) == (size_t)PoolRoute::COUNT, "one name per route");
+  TFA_CHECK((int)r >= 0 && r < PoolRoute::COUNT, "pool route ", (int)r, " out of range");
+  return names[(int)r];
 }
 
-void gemm_f64_launch(const GemmArgs& g, hipStream_t s) {
+void set_pool_route(int route) {
+  TFA_CHECK(route >= -1 && route < (int)PoolRoute::COUNT, "set_pool_route: route ", route, " out of range");
+  forced_pool_route().store(route);
+}
+
+PoolPlan pool_route(const PoolArgs& a, bool x_aligned16, bool y_aligned16) {
+  static const bool env_generic = [] {
+    const char* e = std::getenv("TFA_POOL_GENERIC");
+    return e && e[0] == '1';
+  }();
+  static const bool env_no_xcd = [] {
+    const char* e = std::getenv("TFA_POOL_XCD");
+    return e && e[0] == '0';
+  }();
+  // what the shape allows
+  PoolNeeds can;
+  can.v4 = a.C % 4 == 0 && x_aligned16 && y_aligned16 && a.ldc % 4 == 0;
+  const int64_t out_span = a.ldc ? a.N * a.OH * a.OW * a.ldc : a.N * a.OH * a.OW * a.C;
+  can.u32 = a.N * a.H * a.W * a.C < (int64_t(1) << 31) && a.N * a.OH * a.OW * a.C < (int64_t(1) << 31);
+  can.k3 = can.v4 && can.u32 && a.KH == 3 && a.KW == 3 && out_span < (int64_t(1) << 31);
+  can.xcd = can.k3 && (a.N * a.OH * a.OW * (a.C / 4) + 255) / 256 < (int64_t(1) << 30);
+  PoolNeeds use = can;
+  if (env_generic) use.k3 = false;
+  if (env_no_xcd) use.xcd = false;
+  const int forced = forced_pool_route().load();
+  if (forced >= 0) {
+    const PoolNeeds f = pool_needs((PoolRoute)forced);
+    TFA_CHECK((!f.k3 || can.k3) && (!f.xcd || can.xcd) && (!f.u32 || can.u32) && (!f.v4 || can.v4),
+              "pool2d: forced route ", pool_route_name((PoolRoute)forced),
+              " is more specialised than this pool allows (only 3x3 -> generic, xcd -> plain grid, u32 -> i64 and "
+              "v4 -> v1 can be forced)");
+    use = f;
+  }
+  PoolPlan p;
+  p.V = use.v4 ? 4 : 1;
+  p.items = a.N * a.OH * a.OW * (a.C / p.V);
+  p.blocks = ew_grid(p.items);
+  if (use.k3) {
+    p.route = use.xcd ? PoolRoute::P3X3_V4_XCD : PoolRoute::P3X3_V4;
+    if (use.xcd) p.blocks = (p.items + 255) / 256;  // one block per 256 items, XCD-remapped
+  } else if (use.v4) {
+    p.route = use.u32 ? PoolRoute::GENERIC_V4_U32 : PoolRoute::GENERIC_V4_I64;
+  } else {
+    p.route = use.u32 ? PoolRoute::GENERIC_V1_U32 : PoolRoute::GENERIC_V1_I64;
+  }
+  return p;
+}
+
+const char* gemm_f64_tile_name(F64Tile t) {
+  static const char* const names[] = {"64x16", "64x64", "128x128"};
+  TFA_CHECK((int)t >= 0 && t < F64Tile::COUNT, "f64 tile ", (int)t, " out of range");
+  return names[(int)t];
+}
+
+GemmF64Plan gemm_f64_route(int64_t M, int64_t N, int64_t K, int64_t batch, bool ta, bool tb, int64_t lda,
+                           int64_t ldb, bool a_aligned16, bool b_aligned16) {
+  (void)ta;
+  (void)tb;  // the four <TA, TB> kernels share one tiling
+  GemmF64Plan p;
   // 128x128 tiles halve operand traffic per FLOP; used when they still give
   // >= 2 blocks per CU (256 CUs), else 64x64
   // skinny N (K-Means: points x k centres): 64x16 tiles, A streamed once by
   // many blocks (the shape is HBM-bound)
-  const int64_t big = ((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
-  if (g.N <= 16) gemm_f64_tile_launch<64, 16, 4, 1>(g, s);
-  else if (g.N > 64 && big >= 512) gemm_f64_tile_launch<128, 128, 2, 2>(g, s);
-  else gemm_f64_tile_launch<64, 64, 2, 2>(g, s);
+  const int64_t big = ((M + 127) / 128) * ((N + 127) / 128) * batch;
+  if (N <= 16) { p.tile = F64Tile::T64x16; p.BM = 64; p.BN = 16; }
+  else if (N > 64 && big >= 512) { p.tile = F64Tile::T128x128; p.BM = 128; p.BN = 128; }
+  else { p.tile = F64Tile::T64x64; p.BM = 64; p.BN = 64; }
+  p.tiles_m = (M + p.BM - 1) / p.BM;
+  p.tiles_n = (N + p.BN - 1) / p.BN;
+  TFA_CHECK(p.tiles_m * p.tiles_n < (int64_t(1) << 31), "gemm: grid too large");
+  p.launches = (batch + kGemmMaxBatchPerLaunch - 1) / kGemmMaxBatchPerLaunch;
+  p.k_mult16 = K > 0 && K % D_BK == 0;
+  p.a_pairs = a_aligned16 && lda % 2 == 0;
+  p.b_pairs = b_aligned16 && ldb % 2 == 0;
+  return p;
+}
+
+GemmIntPlan gemm_int_route(int64_t M, int64_t N, int64_t K, int64_t batch) {
+  (void)K;
+  GemmIntPlan p;
+  p.tiles_m = (M + 15) / 16;
+  p.tiles_n = (N + 15) / 16;
+  TFA_CHECK(p.tiles_m * p.tiles_n < (int64_t(1) << 31), "int gemm: grid too large");
+  p.launches = (batch + kGemmMaxBatchPerLaunch - 1) / kGemmMaxBatchPerLaunch;
+  return p;
+}
+
+template <int BM, int BN, int WM, int WN>
+static void gemm_f64_tile_launch(const GemmArgs& g, const GemmF64Plan& p, hipStream_t s) {
+  const int tm = (int)p.tiles_m, tn = (int)p.tiles_n;
+  for (int64_t b0 = 0; b0 < g.batch; b0 += kGemmMaxBatchPerLaunch) {
+    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)std::min(g.batch - b0, kGemmMaxBatchPerLaunch));
+    if (!g.ta && !g.tb) hipLaunchKernelGGL((gemm_f64_mfma<BM, BN, WM, WN, false, false>), grid, dim3(256), 0, s, g, tm, tn, b0);
+    else if (!g.ta && g.tb) hipLaunchKernelGGL((gemm_f64_mfma<BM, BN, WM, WN, false, true>), grid, dim3(256), 0, s, g, tm, tn, b0);
+    else if (g.ta && !g.tb) hipLaunchKernelGGL((gemm_f64_mfma<BM, BN, WM, WN, true, false>), grid, dim3(256), 0, s, g, tm, tn, b0);
+    else hipLaunchKernelGGL((gemm_f64_mfma<BM, BN, WM, WN, true, true>), grid, dim3(256), 0, s, g, tm, tn, b0);
+  }
+}
+
+void gemm_f64_launch(const GemmArgs& g, hipStream_t s) {
+  const GemmF64Plan p = gemm_f64_route(g.M, g.N, g.K, g.batch, g.ta, g.tb, g.lda, g.ldb,
+                                       (reinterpret_cast<uintptr_t>(g.A) & 15) == 0,
+                                       (reinterpret_cast<uintptr_t>(g.B) & 15) == 0);
+  switch (p.tile) {
+    case F64Tile::T64x16: gemm_f64_tile_launch<64, 16, 4, 1>(g, p, s); break;
+    case F64Tile::T128x128: gemm_f64_tile_launch<128, 128, 2, 2>(g, p, s); break;
+    default: gemm_f64_tile_launch<64, 64, 2, 2>(g, p, s); break;
+  }
 }
 
 void gemm_int_launch(DType dt, const GemmArgs& g, hipStream_t s) {
-  dim3 grid((unsigned)((g.N + 15) / 16), (unsigned)((g.M + 15) / 16), (unsigned)g.batch);
-  TFA_CHECK((g.M + 15) / 16 <= 65535, "int gemm: M too large");
-  if (dt == DType::I32) hipLaunchKernelGGL((gemm_int<int32_t>), grid, dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((gemm_int<int64_t>), grid, dim3(256), 0, s, g);
+  const GemmIntPlan p = gemm_int_route(g.M, g.N, g.K, g.batch);
+  for (int64_t b0 = 0; b0 < g.batch; b0 += kGemmMaxBatchPerLaunch) {
+    const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)std::min(g.batch - b0, kGemmMaxBatchPerLaunch));
+    if (dt == DType::I32) hipLaunchKernelGGL((gemm_int<int32_t>), grid, dim3(256), 0, s, g, (int)p.tiles_n, b0);
+    else hipLaunchKernelGGL((gemm_int<int64_t>), grid, dim3(256), 0, s, g, (int)p.tiles_n, b0);
+  }
 }
 
 void pool2d_nhwc(DType dt, const PoolArgs& a, hipStream_t s) {

@@ -251,11 +251,16 @@ __global__ __launch_bounds__(kT) void mod_kernel(const uint64_t* __restrict__ h,
     dest[i] = (int64_t)(h[i] % (uint64_t)world);
 }
 
-// rep[ids[i]] = i: any row of a group represents it (concurrent writers all
-// store valid rows of the same group)
-__global__ __launch_bounds__(kT) void rep_kernel(const int64_t* __restrict__ ids, int64_t n, int64_t* __restrict__ rep) {
+// rep[ids[i]] = max i: the last row of a group represents it, as the host
+// path's `rep[ids] = arange(n)` leaves it, so that both give the same bits
+// where the rows of a group differ in them (-0.0 and 0.0, the NaNs). rep
+// starts at 0; the plain read spares most rows the atomic.
+__global__ __launch_bounds__(kT) void rep_kernel(const int64_t* __restrict__ ids, int64_t n, int64_t* rep) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) rep[ids[i]] = i;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    unsigned long long* r = reinterpret_cast<unsigned long long*>(rep + ids[i]);
+    if (*reinterpret_cast<volatile unsigned long long*>(r) < (unsigned long long)i) atomicMax(r, (unsigned long long)i);
+  }
 }
 
 // ---------------------------------------------------------------- segment CSR
@@ -532,8 +537,9 @@ void segment_csr(DType idt, const void* ids, int64_t n, int64_t nseg, int64_t* p
   TFA_LAUNCH_CHECK("segment_csr");
 }
 
-void group_representatives(const int64_t* ids, int64_t n, int64_t* rep, hipStream_t s) {
-  if (n == 0) return;
+void group_representatives(const int64_t* ids, int64_t n, int64_t nseg, int64_t* rep, hipStream_t s) {
+  if (n == 0 || nseg == 0) return;
+  hipLaunchKernelGGL(zero_i64_kernel, dim3(ew_grid(nseg)), dim3(kT), 0, s, rep, nseg);
   hipLaunchKernelGGL(rep_kernel, dim3(ew_grid(n)), dim3(kT), 0, s, ids, n, rep);
 }
 

@@ -47,11 +47,13 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDivU32& f) {
 
 // the cheap epilogue activations (none / relu / relu6): kernels branch once
 // on `act` between an epilogue built from this and one built from act_apply,
-// so the transcendental forms do not bloat the common hot epilogue
+// so the transcendental forms do not bloat the common hot epilogue.
+// A NaN stays NaN, as clamp_min / clamp of the host executor keep it: the
+// compares are written so that a NaN takes the `v` branch.
 template <typename T>
 __device__ __forceinline__ T act_fast(T v, int act) {
-  if (act == ACT_RELU) return v > T(0) ? v : T(0);
-  if (act == ACT_RELU6) return v > T(0) ? (v < T(6) ? v : T(6)) : T(0);
+  if (act == ACT_RELU) return v < T(0) ? T(0) : v;
+  if (act == ACT_RELU6) return v < T(0) ? T(0) : (v > T(6) ? T(6) : v);
   return v;
 }
 
@@ -60,8 +62,8 @@ __device__ __forceinline__ T act_fast(T v, int act) {
 template <typename T>
 __device__ __forceinline__ T act_apply(T v, int act) {
   switch (act) {
-    case ACT_RELU: return v > T(0) ? v : T(0);
-    case ACT_RELU6: return v > T(0) ? (v < T(6) ? v : T(6)) : T(0);
+    case ACT_RELU: return v < T(0) ? T(0) : v;  // NaN stays NaN (see act_fast)
+    case ACT_RELU6: return v < T(0) ? T(0) : (v > T(6) ? T(6) : v);
     case ACT_SIGMOID: return T(1) / (T(1) + exp(-v));
     case ACT_TANH: return tanh(v);
     case ACT_ELU: return v > T(0) ? v : expm1(v);

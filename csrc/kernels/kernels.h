@@ -157,8 +157,8 @@ void segment_csr(DType idt, const void* ids, int64_t n, int64_t nseg, int64_t* p
 // segment g = rows perm[offsets[g] .. offsets[g+1]) of x [*, inner] -> y [nseg, inner] (deterministic)
 void segment_reduce_perm(RedOp op, DType dt, const void* x, const int64_t* perm, const int64_t* offsets, void* y,
                          int64_t nseg, int64_t inner, hipStream_t s);
-// rep[g] = some row of group g (ids in [0, nseg))
-void group_representatives(const int64_t* ids, int64_t n, int64_t* rep, hipStream_t s);
+// rep[g] = the last row of group g (ids in [0, nseg)), as the host path picks it
+void group_representatives(const int64_t* ids, int64_t n, int64_t nseg, int64_t* rep, hipStream_t s);
 // idx[g * size + j] = perm[offs[g] + j]: row ids of G segments of one size
 void segment_rows(const int64_t* perm, const int64_t* offs, int64_t G, int64_t size, int64_t* idx, hipStream_t s);
 // dst row idx[j] = src row j (rows of row_bytes bytes)
@@ -524,6 +524,34 @@ void gemm_tune_seed(const std::vector<int64_t>& key, int cfg);
 void gemm_tune_reset();
 std::vector<int> gemm_tile_dims(int cfg);  // {BM, BN, core (1 round-4, 2 g2)}
 int f32_precision();
+// The launch one float64 GEMM takes (gemm_f64.hip): plain host code, no
+// device, as reduce_route. The launch code switches on it and the tests read
+// it. Whether a block is interior (unchecked 16-byte pair loads) or an edge
+// block (checked loads) is decided on the device per block: a block loads A in
+// pairs when its BM rows are in range and `a_pairs` holds, B likewise, and it
+// runs the interleaved FAST loop when both do and `k_mult16` holds.
+enum class F64Tile : int { T64x16, T64x64, T128x128, COUNT };
+constexpr int64_t kGemmMaxBatchPerLaunch = 65535;  // grid.z
+struct GemmF64Plan {
+  F64Tile tile;
+  int BM, BN;
+  int64_t tiles_m, tiles_n;  // grid.x = tiles_m * tiles_n (XCD-remapped), grid.y = 1
+  int64_t launches;          // slices of at most kGemmMaxBatchPerLaunch batches (grid.z)
+  bool k_mult16;             // K > 0 && K % 16 == 0
+  bool a_pairs, b_pairs;     // the operand is 16-byte aligned and its leading dimension even
+};
+const char* gemm_f64_tile_name(F64Tile t);
+// a_aligned16 / b_aligned16: the operand's base address (of batch 0; a batch
+// whose stride is odd moves every other matrix off the pair loads)
+GemmF64Plan gemm_f64_route(int64_t M, int64_t N, int64_t K, int64_t batch, bool ta, bool tb, int64_t lda,
+                           int64_t ldb, bool a_aligned16, bool b_aligned16);
+// The integer GEMM: 16x16 output tiles, row-major over grid.x (column tile
+// fastest), batches in grid.z slices as above.
+struct GemmIntPlan {
+  int64_t tiles_m, tiles_n;  // grid.x = tiles_m * tiles_n < 2^31
+  int64_t launches;
+};
+GemmIntPlan gemm_int_route(int64_t M, int64_t N, int64_t K, int64_t batch);
 
 // ------------------------------------------------------------ conv / pool (NHWC)
 struct ConvArgs {
@@ -566,6 +594,31 @@ struct PoolArgs {
   int64_t ldc = 0;             // 0 = C
 };
 void pool2d_nhwc(DType dt, const PoolArgs& a, hipStream_t s);
+// The kernel one pool2d_nhwc() call takes (host only, as reduce_route). From
+// the most to the least specialised: the unrolled 3x3 kernel (float4 channels,
+// 32-bit indices) on the XCD-remapped or the plain grid, then the generic
+// window loop with float4 (V4) or scalar (V1) channels and 32- or 64-bit
+// index math.
+enum class PoolRoute : int {
+  P3X3_V4_XCD, P3X3_V4, GENERIC_V4_U32, GENERIC_V4_I64, GENERIC_V1_U32, GENERIC_V1_I64, COUNT
+};
+struct PoolPlan {
+  PoolRoute route;
+  int V;           // channels per item
+  int64_t items;   // N * OH * OW * C / V
+  int64_t blocks;  // grid.x
+};
+const char* pool_route_name(PoolRoute r);
+// Only N, H, W, C, OH, OW, KH, KW and ldc of `a` are read. The result honours
+// TFA_POOL_GENERIC=1 / TFA_POOL_XCD=0 and set_pool_route().
+PoolPlan pool_route(const PoolArgs& a, bool x_aligned16, bool y_aligned16);
+// Force a route process-wide (-1: automatic), for tests: the 64-bit index
+// kernels and the plain-grid 3x3 kernel are otherwise reached only from 2^31
+// elements / 2^30 blocks upward. Only a less specialised route than the
+// automatic one can be forced (3x3 -> generic, xcd -> plain grid, u32 -> i64,
+// v4 -> v1); pool_route() raises where the forced route asks for more than the
+// shape allows.
+void set_pool_route(int route);
 // VALID 3x3 max pool (any stride) feeding a 1x1 / stride-1 conv (+ bias + act) in one kernel
 // (conv_smallc.hip): Inception-v3 MaxPool_3a -> Conv2d_3b. The pooled tensor
 // never reaches HBM. x: the pool's NHWC input; w: [C][OC]; y: [N*PH*PW][ldc].

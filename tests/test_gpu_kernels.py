@@ -234,9 +234,14 @@ def test_matmul_f64_mfma(m, n, k):
         tf.matmul(a, b, transpose_b=True, name="c")
     a_ = rng.uniform(-1, 1, (m, k))
     b_ = rng.uniform(-1, 1, (n, k))
-    got = run(g, ["c"], {"a": a_, "b": b_})[0]
-    want = torch.as_tensor(a_) @ torch.as_tensor(b_).T
-    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-11)
+    got = run(g, ["c"], {"a": a_, "b": b_})[0].cpu().numpy()
+    # the bound of any order of K FMAs: |got - want| <= gamma_K (|A| @ |B|), gamma_K = K u / (1 - K u), u = 2^-53,
+    # against a long double product
+    want = np.matmul(a_.astype(np.longdouble), b_.T.astype(np.longdouble))
+    u = 2.0 ** -53
+    bound = k * u / (1 - k * u) * (np.abs(a_) @ np.abs(b_).T)
+    err = np.abs(got.astype(np.longdouble) - want).astype(np.float64)
+    assert got.shape == (m, n) and (err <= bound).all(), float((err / bound).max())
 
 
 def test_fused_gemm_bias_relu_identity_asymmetric():
