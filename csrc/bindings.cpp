@@ -12,6 +12,7 @@
 #include "kernels/kernels.h"
 #include "runtime/device_pool.h"
 #include "runtime/executor.h"
+#include "runtime/fusion.h"
 #include "runtime/jit.h"
 #include "runtime/jpeg_decode.h"
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -1642,6 +1643,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     d["compile_ms"] = s.compile_ms;
     return d;
   });
+  m.def("fusible_ops", [] {
+    py::dict d;
+    for (auto& o : tfa::fusible_ops()) {
+      py::dict e;
+      e["kind"] = std::string(o.kind);
+      e["float_only"] = o.float_only;
+      d[py::str(o.op)] = e;
+    }
+    return d;
+  }, "every op the fusion generator can emit: name -> {kind: unary | binary | cast | view | broadcast, float_only}");
+  m.def("set_fusion_index64", [](py::object on) { tfa::set_fusion_index64(!on.is_none() && on.cast<bool>()); },
+        py::arg("on"),
+        "True: every generated fusion kernel of a plan made from now on indexes with 64 bits, whatever its size "
+        "(elementwise regions and row reductions); None or False: the automatic choice (64-bit from 2^31 elements). "
+        "Read at planning time. The setting is part of the key of each program's plan cache, so a plan made under "
+        "one setting is not served under the other; the generated sources differ, so the kernel cache needs nothing.");
   m.def("set_debug_sync", &set_debug_sync, "synchronise + check after every kernel (read per launch)");
   m.def("get_debug_sync", &get_debug_sync);
   m.def("f32_precision", [] { return k::f32_precision(); });

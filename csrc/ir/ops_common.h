@@ -117,7 +117,7 @@ inline at::Tensor apply_act_host(const at::Tensor& r, int act) {
     case k::ACT_TANH: return at::tanh(r);
     case k::ACT_ELU: return at::where(r > 0, r, at::expm1(r));
     case k::ACT_SELU: return at::selu(r);
-    case k::ACT_SOFTPLUS: return at::where(r > 20, r, at::log1p(at::exp(r)));
+    case k::ACT_SOFTPLUS: return at::clamp_min(r, 0) + at::log1p(at::exp(-at::abs(r)));  // as the kernels: no threshold
     default: return r;
   }
 }

@@ -128,7 +128,9 @@ at::Tensor cpu_unary(k::UnOp op, const at::Tensor& x) {
     case k::UnOp::SELU: return at::selu(x);
     case k::UnOp::SIGMOID: return at::sigmoid(x);
     case k::UnOp::TANH: return at::tanh(x);
-    case k::UnOp::SOFTPLUS: return at::softplus(x);
+    // max(x, 0) + log1p(exp(-|x|)), the form of the kernels: at::softplus returns x above 20, which in
+    // float64 is wrong by up to 2e5 ulp
+    case k::UnOp::SOFTPLUS: return at::clamp_min(x, 0) + at::log1p(at::exp(-at::abs(x)));
     case k::UnOp::SOFTSIGN: return at::div(x, at::abs(x) + 1);
     case k::UnOp::FLOOR: return at::floor(x);
     case k::UnOp::CEIL: return at::ceil(x);
@@ -192,7 +194,8 @@ at::Tensor cpu_reduce(k::RedOp op, const at::Tensor& x, const std::vector<int64_
       if (at::isFloatingType(st)) return at::mean(x, axes, keep);
       int64_t cnt = 1;
       for (auto a : axes) cnt *= x.size(a);
-      return at::div(at::sum(x, axes, keep, st), cnt, "trunc").to(st);
+      // the 64-bit sum divided with truncation, as the device kernels: an int32 sum does not wrap first
+      return at::div(at::sum(x, axes, keep, at::kLong), cnt, "trunc").to(st);
     }
     case k::RedOp::ALL: {
       at::Tensor r = x.to(at::kBool);

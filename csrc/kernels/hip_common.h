@@ -71,7 +71,7 @@ __device__ __forceinline__ T act_apply(T v, int act) {
       const T alpha = T(1.6732632423543772848170429916717), scale = T(1.0507009873554804934193349852946);
       return v > T(0) ? scale * v : scale * alpha * expm1(v);
     }
-    case ACT_SOFTPLUS: return v > T(20) ? v : log1p(exp(v));
+    case ACT_SOFTPLUS: return (v > T(0) ? v : T(0)) + log1p(exp(-fabs(v)));  // as un_apply: no threshold
     default: return v;
   }
 }
@@ -118,7 +118,10 @@ __device__ __forceinline__ T epi_apply(const EpiProg& e, T v, int64_t row, int64
       case EPI_ACT: v = act_apply(v, o.act); break;
       case EPI_NEG: v = -v; break;
       case EPI_SQUARE: v = v * v; break;
-      case EPI_ABS: v = v < T(0) ? -v : v; break;
+      case EPI_ABS:  // abs(-0.0) is +0.0, as un_apply and the host
+        if constexpr (std::is_floating_point<T>::value) v = fabs(v);
+        else v = v < T(0) ? -v : v;
+        break;
       default: break;
     }
   }

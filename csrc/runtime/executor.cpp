@@ -541,6 +541,7 @@ static std::string plan_key(const std::vector<at::Tensor>& inputs) {
     for (auto d : t.sizes()) os << d << ',';
     os << ']';
   }
+  if (fusion_index64()) os << "|idx64";  // set_fusion_index64: regions are generated differently
   return os.str();
 }
 
@@ -2689,7 +2690,14 @@ std::string Program::describe_plan(const std::vector<at::Tensor>& inputs, bool a
     if (st.kind == Step::FUSED) {
       const FusedRegion& rg = p->fused_regions[st.fused]->region;
       os << "  FUSED" << (rg.kind == 1 ? "-ROWRED " : " ") << nd.name << " [" << rg.expr << "] "
-         << rg.leaves.size() << " inputs " << rg.outputs.size() << " outputs " << st.out_info[0].shape.str() << '\n';
+         << rg.leaves.size() << " inputs " << rg.outputs.size() << " outputs " << st.out_info[0].shape.str();
+      // the route: index width, thread or wave per row, and how each leaf is read
+      os << (rg.idx64 ? " idx64" : " idx32");
+      if (rg.kind == 1) os << (rg.wave ? " wave" : " thread");
+      os << " leaves[";
+      static const char* leaf_kinds[] = {"contiguous", "scalar", "strided"};
+      for (size_t k = 0; k < rg.leaves.size(); ++k) os << (k ? "," : "") << leaf_kinds[rg.leaves[k].kind];
+      os << "]\n";
       continue;
     }
     os << "  " << (st.kind == Step::GEMM ? "GEMM" : st.kind == Step::CONV ? "CONV" : "OP  ") << ' '

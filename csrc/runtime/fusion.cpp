@@ -2,6 +2,7 @@
 #include "fusion.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <functional>
 #include <sstream>
@@ -19,21 +20,23 @@ struct OpSpec {
 
 const std::map<std::string, OpSpec>& op_table() {
   // Formulas mirror the unfused kernels (kernels/elementwise.hip un_apply /
-  // bin_arith) so a fused region computes what the op-by-op plan computes.
+  // bin_arith) so a fused region computes what the op-by-op plan computes, bit
+  // for bit (tests/test_gpu_fusion_routes.py): a NaN stays NaN through Relu /
+  // Relu6, abs(-0.0) is +0.0, Softplus has no threshold.
   static const std::map<std::string, OpSpec> t = {
       {"Neg", {Kind::UNARY, "(-{0})", false}},
-      {"Abs", {Kind::UNARY, "({0} < ({T})0 ? -{0} : {0})", false}},
+      {"Abs", {Kind::UNARY, "tfa_abs({0})", false}},
       {"Square", {Kind::UNARY, "({0} * {0})", false}},
       {"Sqrt", {Kind::UNARY, "sqrt({0})", true}},
       {"Rsqrt", {Kind::UNARY, "(({T})1 / sqrt({0}))", true}},
       {"Exp", {Kind::UNARY, "exp({0})", true}},
-      {"Log", {Kind::UNARY, "log({0})", true}},
+      {"Log", {Kind::UNARY, "tfa_log({0})", true}},
       {"Log1p", {Kind::UNARY, "log1p({0})", true}},
       {"Expm1", {Kind::UNARY, "expm1({0})", true}},
       {"Reciprocal", {Kind::UNARY, "(({T})1 / {0})", true}},
       {"Inv", {Kind::UNARY, "(({T})1 / {0})", true}},
-      {"Relu", {Kind::UNARY, "({0} > ({T})0 ? {0} : ({T})0)", false}},
-      {"Relu6", {Kind::UNARY, "({0} > ({T})0 ? ({0} < ({T})6 ? {0} : ({T})6) : ({T})0)", false}},
+      {"Relu", {Kind::UNARY, "({0} < ({T})0 ? ({T})0 : {0})", false}},
+      {"Relu6", {Kind::UNARY, "({0} < ({T})0 ? ({T})0 : ({0} > ({T})6 ? ({T})6 : {0}))", false}},
       {"Elu", {Kind::UNARY, "({0} > ({T})0 ? {0} : expm1({0}))", true}},
       {"Selu", {Kind::UNARY,
                 "({0} > ({T})0 ? ({T})1.0507009873554804934193349852946 * {0} : "
@@ -41,7 +44,7 @@ const std::map<std::string, OpSpec>& op_table() {
                 true}},
       {"Sigmoid", {Kind::UNARY, "(({T})1 / (({T})1 + exp(-{0})))", true}},
       {"Tanh", {Kind::UNARY, "tanh({0})", true}},
-      {"Softplus", {Kind::UNARY, "({0} > ({T})20 ? {0} : log1p(exp({0})))", true}},
+      {"Softplus", {Kind::UNARY, "(({0} > ({T})0 ? {0} : ({T})0) + log1p(exp(-fabs({0}))))", true}},
       {"Softsign", {Kind::UNARY, "({0} / (({T})1 + fabs({0})))", true}},
       {"Floor", {Kind::UNARY, "floor({0})", true}},
       {"Ceil", {Kind::UNARY, "ceil({0})", true}},
@@ -336,7 +339,19 @@ std::string preamble(const std::string& desc, bool idx64, int words) {
        " return (a != a || b != b) ? (a + b) : (a > b ? a : b); }\n"
     << "template <typename T> __device__ __forceinline__ T tfa_min(T a, T b) {"
        " return (a != a || b != b) ? (a + b) : (a < b ? a : b); }\n"
-    << "template <typename T> __device__ __forceinline__ T tfa_sqd(T a, T b) { T d = a - b; return d * d; }\n";
+    << "template <typename T> __device__ __forceinline__ T tfa_sqd(T a, T b) { T d = a - b; return d * d; }\n"
+    // abs(-0.0) is +0.0, as at::abs on the host
+    << "__device__ __forceinline__ float tfa_abs(float a) { return __builtin_fabsf(a); }\n"
+    << "__device__ __forceinline__ double tfa_abs(double a) { return __builtin_fabs(a); }\n"
+    << "__device__ __forceinline__ int tfa_abs(int a) { return a < 0 ? -a : a; }\n"
+    << "__device__ __forceinline__ long long tfa_abs(long long a) { return a < 0 ? -a : a; }\n"
+    // The float log is expanded by the compiler (v_log_f32 times ln 2 in two parts); the kernel library is
+    // built with contraction on, where the last add of that expansion fuses into an fma. These kernels are
+    // built with contraction off (x * y + z must round twice, as two kernels do), so the one function asks
+    // for it locally and gives the library's bits.
+    << "__device__ __forceinline__ float tfa_log(float a) {\n#pragma clang fp contract(fast)\n"
+       "  return __builtin_logf(a);\n}\n"
+    << "__device__ __forceinline__ double tfa_log(double a) { return log(a); }\n";
   return s.str();
 }
 
@@ -480,12 +495,17 @@ std::string generate_reduce_source(FusedRegion& r, const Gen* gen, const std::st
     const std::string& op = r.red_ops[k];
     if (op == "Sum" || op == "Mean") s << "    acc" << k << " += (" << A << ")x;\n";
     else if (op == "Prod") s << "    acc" << k << " *= (" << A << ")x;\n";
-    else if (op == "Min") s << "    acc" << k << " = (" << A << ")x < acc" << k << " ? (" << A << ")x : acc" << k << ";\n";
-    else if (op == "Max") s << "    acc" << k << " = (" << A << ")x > acc" << k << " ? (" << A << ")x : acc" << k << ";\n";
-    else {
+    else if (op == "Min" || op == "Max") {
+      // a NaN propagates: it replaces the accumulator, and no later value replaces a NaN
+      const char* cmp = op == "Min" ? "<" : ">";
+      s << "    acc" << k << " = (x != x || (" << A << ")x " << cmp << " acc" << k << ") ? (" << A << ")x : acc" << k
+        << ";\n";
+    } else {
+      // the first NaN wins ArgMax and ArgMin alike (reduce.hip and numpy do the same); j ascends, so a NaN
+      // already held is the lane's first
       const char* cmp = op == "ArgMin" ? "<" : ">";
-      s << "    if (bi" << k << " == (idx_t)-1 || x " << cmp << " best" << k << ") { best" << k << " = x; bi" << k
-        << " = j; }\n";
+      s << "    if (bi" << k << " == (idx_t)-1 || (best" << k << " == best" << k << " && (x != x || x " << cmp
+        << " best" << k << "))) { best" << k << " = x; bi" << k << " = j; }\n";
     }
   }
   s << "  }\n";
@@ -497,15 +517,19 @@ std::string generate_reduce_source(FusedRegion& r, const Gen* gen, const std::st
       else if (op == "Prod") s << "    acc" << k << " *= __shfl_xor(acc" << k << ", off, 64);\n";
       else if (op == "Min" || op == "Max") {
         const char* cmp = op == "Min" ? "<" : ">";
-        s << "    { const " << A << " o = __shfl_xor(acc" << k << ", off, 64); acc" << k << " = o " << cmp << " acc" << k
-          << " ? o : acc" << k << "; }\n";
+        s << "    { const " << A << " o = __shfl_xor(acc" << k << ", off, 64); acc" << k << " = (o != o || o " << cmp
+          << " acc" << k << ") ? o : acc" << k << "; }\n";
       } else {
-        // first index among equal values; an empty lane (bi == -1) never wins
+        // first index among equal values, and among NaNs, which beat every number; an empty lane
+        // (bi == -1) never wins
         const char* cmp = op == "ArgMin" ? "<" : ">";
         s << "    { const " << T << " ob = __shfl_xor(best" << k << ", off, 64); const idx_t oi = __shfl_xor(bi" << k
           << ", off, 64);\n"
-          << "      if (oi != (idx_t)-1 && (bi" << k << " == (idx_t)-1 || ob " << cmp << " best" << k << " || (ob == best"
-          << k << " && oi < bi" << k << "))) { best" << k << " = ob; bi" << k << " = oi; } }\n";
+          << "      const bool on = ob != ob, bn = best" << k << " != best" << k << ";\n"
+          << "      const bool better = on ? (!bn || oi < bi" << k << ") : (!bn && (ob " << cmp << " best" << k
+          << " || (ob == best" << k << " && oi < bi" << k << ")));\n"
+          << "      if (oi != (idx_t)-1 && (bi" << k << " == (idx_t)-1 || better)) { best" << k << " = ob; bi" << k
+          << " = oi; } }\n";
       }
     }
     s << "  }\n  if (lane != 0) return;\n";
@@ -529,6 +553,19 @@ bool is_reduction_op(const std::string& op) {
 }  // namespace
 
 bool fusible_op(const std::string& op) { return op_table().count(op) > 0; }
+
+std::vector<FusibleOp> fusible_ops() {
+  static const char* kinds[] = {"unary", "binary", "view", "broadcast", "cast"};  // enum Kind order
+  std::vector<FusibleOp> v;
+  for (auto& [name, s] : op_table()) v.push_back({name, kinds[static_cast<int>(s.kind)], s.float_only});
+  return v;
+}
+
+namespace {
+std::atomic<bool> g_force_index64{false};
+}
+void set_fusion_index64(bool force) { g_force_index64 = force; }
+bool fusion_index64() { return g_force_index64; }
 
 bool fusion_enabled() {
   static const bool on = [] {
@@ -619,7 +656,7 @@ std::vector<FusedRegion> find_fused_regions(const FusionInput& in) {
     const TensorInfo& ai = f.info(nd.inputs[1]);
     const TensorInfo& oi = f.infos[n][0];
     if (!value_dtype(xi.dtype) || !xi.shape.fully_known() || !ai.value || !oi.shape.fully_known()) continue;
-    if (nd.op == "Mean" && !(xi.dtype == DType::F32 || xi.dtype == DType::F64) && false) continue;
+    // an integer Mean fuses too: the 64-bit sum divided with truncation, as reduce.hip and the host compute it
     const int rank = xi.shape.rank();
     if (rank < 2) continue;
     std::vector<int64_t> axes = to_int_vector(*ai.value);
@@ -696,8 +733,10 @@ std::vector<FusedRegion> find_fused_regions(const FusionInput& in) {
     for (auto d : odt) ok = ok && value_dtype(d);
     if (!ok) continue;
     r.expr = (prologue ? ops_desc(f.g, r.nodes) + " -> " : std::string()) + ops_desc(f.g, reds);
-    const bool idx64 = std::max(r.numel, max_leaf) >= (int64_t(1) << 31);
+    const bool idx64 = fusion_index64() || std::max(r.numel, max_leaf) >= (int64_t(1) << 31);
     const bool wave = r.inner > 16;
+    r.idx64 = idx64;
+    r.wave = wave;
     r.entry = "tfa_fused_rowred";
     r.block = 256;
     r.grid = wave ? (r.outer + 3) / 4 : (r.outer + 255) / 256;
@@ -739,7 +778,8 @@ std::vector<FusedRegion> find_fused_regions(const FusionInput& in) {
     int64_t max_leaf = 0;
     finish_leaves(f, r, gen, root_dims, 0, &max_leaf);
     r.expr = ops_desc(f.g, r.nodes);
-    const bool idx64 = std::max(r.numel, max_leaf) >= (int64_t(1) << 31);
+    const bool idx64 = fusion_index64() || std::max(r.numel, max_leaf) >= (int64_t(1) << 31);
+    r.idx64 = idx64;
     r.entry = "tfa_fused";
     r.block = kFusedBlock;
     r.grid = (r.numel + int64_t(kFusedBlock) * kFusedEPT - 1) / (int64_t(kFusedBlock) * kFusedEPT);

@@ -57,6 +57,8 @@ struct FusedRegion {
   std::string source;            // generated HIP source
   std::string entry;             // kernel name
   std::string expr;              // readable expression (describe)
+  bool idx64 = false;            // the kernel indexes with 64-bit integers
+  bool wave = false;             // kind 1: one wave per row (inner > 16), else one thread per row
   int block = 256;
   int64_t grid = 1;
 };
@@ -87,5 +89,22 @@ constexpr int kFusedEPT = 4;  // elements per thread
 bool fusion_enabled();
 // the op can be evaluated inside a fused elementwise region (no HBM value)
 bool fusible_op(const std::string& op);
+
+// Every op the generator can emit, in name order, with the facts the region
+// finder switches on: kind is "unary", "binary", "cast", "view" or "broadcast".
+struct FusibleOp {
+  std::string op;
+  const char* kind;
+  bool float_only;
+};
+std::vector<FusibleOp> fusible_ops();
+
+// Index width of generated kernels: false is the automatic choice (64-bit from
+// 2^31 elements of the output or of a leaf), true makes every region index
+// with 64 bits (how the tests run that variant at small shapes). Read when a
+// plan is made; part of the plan cache key (executor.cpp plan_key), so a plan
+// made under one setting is never served under the other.
+void set_fusion_index64(bool force);
+bool fusion_index64();
 
 }  // namespace tfa
