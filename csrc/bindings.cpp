@@ -15,6 +15,7 @@
 #include "runtime/fusion.h"
 #include "runtime/jit.h"
 #include "runtime/jpeg_decode.h"
+#include "runtime/unpack.h"
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 namespace py = pybind11;
@@ -317,7 +318,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         d["plans_adopted"] = s.plans_adopted;
         d["h2d_bytes"] = s.h2d_bytes;
         d["d2h_bytes"] = s.d2h_bytes;
+        d["d2h_dense_bytes"] = s.d2h_dense_bytes;  // what the D2H copies delivered (packed fetches expanded)
         d["chunks"] = s.chunks;
+        d["chunks_packed"] = s.chunks_packed;
         d["wall_ms"] = s.wall_ms;
         d["plan_ms"] = s.plan_ms;
         d["exec_ms"] = s.exec_ms;
@@ -2179,6 +2182,72 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("columns"), "row concatenations of several columns into one pool buffer (views of it)");
   m.def("pipeline_wait", &pipeline_wait, py::arg("handle"), py::call_guard<py::gil_scoped_release>(),
         "wait for a run_chunked(wait=False) completion handle (and release it)");
+  // ---- zero-word packing of pipeline outputs (kernels/pack_words.hip, runtime/unpack.cpp)
+  m.def("set_pack_outputs", &set_pack_outputs, py::arg("on"),
+        "run_chunked packs eligible fetches before their D2H copy (config.pack_outputs)");
+  m.def("pack_outputs", &pack_outputs);
+  m.def("set_pack_dense_fraction", &set_pack_dense_fraction, py::arg("t"),
+        "packed / dense size ratio above which a fetch goes back to plain copies (<= 0: the built-in value)");
+  m.def("pack_dense_fraction", &pack_dense_fraction);
+  m.def("pack_layout", [](int64_t rows, int64_t wpr) {
+    const PackLayout L = pack_layout(rows, wpr);
+    py::dict d;
+    d["tile_rows"] = kPackTileRows;
+    d["tiles"] = L.tiles;
+    d["mask_words"] = L.mask_words;
+    d["mask_off"] = L.mask_off;
+    d["values_off"] = L.values_off;
+    d["max_bytes"] = L.max_bytes;
+    return d;
+  }, py::arg("rows"), py::arg("wpr"), "byte layout of a packed rows x wpr buffer (kernels/pack_layout.h)");
+  m.def("pack_words", [](const at::Tensor& src, int64_t rows, int64_t wpr) {
+    TFA_CHECK(src.is_cuda() && src.is_contiguous(), "pack_words: contiguous device tensor expected");
+    TFA_CHECK(rows >= 0 && wpr >= 0 && static_cast<int64_t>(src.numel() * src.element_size()) == rows * wpr * 4,
+              "pack_words: the tensor is not ", rows, " x ", wpr, " words");
+    c10::hip::HIPGuard guard(src.device().index());
+    at::Tensor out = pool_empty({static_cast<int64_t>(k::pack_words_max_bytes(rows, wpr))},
+                                at::TensorOptions().dtype(at::kByte).device(src.device()));
+    k::pack_words(src.data_ptr(), rows, wpr, out.data_ptr(), c10::hip::getCurrentHIPStream(src.device().index()).stream());
+    return out;
+  }, py::arg("src"), py::arg("rows"), py::arg("wpr"),
+        "the packed form (uint8 [max_bytes]; the first 8 bytes are the value word count) of a device buffer");
+  m.def("unpack_words", [](const at::Tensor& packed, at::Tensor& out, int64_t rows, int64_t wpr, int threads) {
+    TFA_CHECK(!packed.is_cuda() && !out.is_cuda() && packed.is_contiguous() && out.is_contiguous(),
+              "unpack_words: contiguous host tensors expected");
+    const PackLayout L = pack_layout(rows, wpr);
+    const size_t have = packed.numel() * packed.element_size();
+    TFA_CHECK(have >= L.values_off, "unpack_words: packed buffer shorter than its header and mask");
+    const uint64_t total = rows && wpr ? *static_cast<const uint64_t*>(packed.data_ptr()) : 0;
+    TFA_CHECK(total <= static_cast<uint64_t>(rows * wpr) && have >= L.values_off + total * 4,
+              "unpack_words: packed buffer shorter than its ", total, " values");
+    TFA_CHECK(static_cast<int64_t>(out.numel() * out.element_size()) == rows * wpr * 4,
+              "unpack_words: the output is not ", rows, " x ", wpr, " words");
+    py::gil_scoped_release nogil;
+    if (threads <= 0) {
+      unpack::unpack_buffer(packed.data_ptr(), out.data_ptr(), rows, wpr, 0, L.tiles);
+    } else {
+      unpack::Pool pool(threads);
+      pool.post_unpack(packed.data_ptr(), out.data_ptr(), rows, wpr)->wait();
+    }
+  }, py::arg("packed"), py::arg("out"), py::arg("rows"), py::arg("wpr"), py::arg("threads") = 0,
+        "expand a packed host buffer into `out` (threads > 0: on a pool of that many workers)");
+  m.def("unpack_force_variant", &unpack::force_variant, py::arg("variant"),
+        "test hook: -1 auto, 0 scalar, 1 AVX2, 2 AVX-512");
+  m.def("unpack_variant_available", &unpack::variant_available, py::arg("variant"));
+  m.def("unpack_current_variant", &unpack::current_variant);
+  m.def("unpack_default_threads", &unpack::default_threads);
+  m.def("unpack_pool_raise", [](int threads, int parts, int bad_part) {
+    py::gil_scoped_release nogil;
+    unpack::Pool pool(threads);
+    pool.post(parts, [bad_part](int p) {
+      if (p == bad_part) throw std::runtime_error("unpack pool test: part " + std::to_string(p) + " failed");
+    })->wait();
+  }, py::arg("threads"), py::arg("parts"), py::arg("bad_part"),
+        "test hook: a pool job whose part `bad_part` throws; the waiter (this call) re-raises it");
+  py::module_::import("atexit").attr("register")(py::cpp_function([] {
+    py::gil_scoped_release nogil;
+    shutdown_pack_runtime();
+  }));
   m.def("device_empty", [](const std::vector<int64_t>& sizes, at::ScalarType dt, int device) {
     c10::hip::HIPGuard guard(static_cast<c10::DeviceIndex>(device));
     return pool_empty(sizes, at::TensorOptions().dtype(dt).device(at::kCUDA, static_cast<c10::DeviceIndex>(device)));

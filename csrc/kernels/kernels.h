@@ -197,6 +197,16 @@ int64_t compact_plan(const uint8_t* mask, int64_t n, void* workspace, size_t wor
 void compact_gather(const PackCols& src, const PackCols& dst, const uint8_t* mask, int64_t n, int64_t total,
                     const void* workspace, int64_t* index, hipStream_t s);
 
+// ------------------------------------------------------------ zero-word packing (pack_words.hip)
+// Packs a contiguous device buffer of rows x wpr 32-bit words into `packed`
+// (pack_layout.h: header, 1-bit-per-word mask, the non-zero words), dropping
+// only words whose bit pattern is 0x00000000. `packed` holds
+// pack_words_max_bytes(rows, wpr) bytes (dense + mask + header: nothing can
+// overflow) and is 64-byte aligned. Asynchronous on `s`; afterwards the first
+// 8 bytes of `packed` hold the number of value words.
+size_t pack_words_max_bytes(int64_t rows, int64_t wpr);
+void pack_words(const void* src, int64_t rows, int64_t wpr, void* packed, hipStream_t s);
+
 // ------------------------------------------------------------ sort (sort.hip)
 // DataFrame.orderBy / sortWithinPartitions. Every sort key becomes one
 // unsigned 64-bit word per row whose unsigned order is the key's order (bool /

@@ -15,6 +15,9 @@
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
+#include <deque>
+#include <thread>
 #include <unistd.h>
 #include <cstdlib>
 #include <set>
@@ -25,6 +28,7 @@
 #include "fusion.h"
 #include "hip_graph.h"
 #include "jit.h"
+#include "unpack.h"
 
 namespace tfa {
 
@@ -2332,6 +2336,163 @@ static void order_copy_after_compute(hipStream_t copy, hipStream_t compute) {
   HIP_OK(hipEventDestroy(e));
 }
 
+// ------------------------------------------------------------------ packed D2H
+// A sparse fetch of run_chunked crosses PCIe packed (kernels/pack_words.hip:
+// a 1-bit-per-word mask plus its non-zero words) into a pinned staging slot
+// and is expanded into the caller's output by the host unpack pool
+// (unpack.cpp). A PackLanding is one such chunk on its way: the completion
+// thread waits for its D2H event (the only HIP call it ever makes), then posts
+// the expansion; whoever needs the staging slot or the outputs waits for it.
+
+// a chunk whose packed size is above this fraction of its dense size is not
+// worth packing (docs/PERFORMANCE.md, "Packed D2H": the threshold sweep;
+// set_pack_dense_fraction is for that sweep)
+constexpr double kPackDenseFraction = 0.782;  // wins at 0.7815 (25 % zero words), not at 1.03
+std::atomic<double> g_pack_dense_fraction{kPackDenseFraction};
+constexpr int kPackStages = 3;
+
+struct PackLanding {
+  struct Task {
+    const void* packed;
+    void* out;
+    int64_t rows, wpr;
+  };
+  hipEvent_t ev = nullptr;  // after the chunk's packed D2H; owned by the Pipe
+  std::vector<Task> tasks;
+
+  // until the chunk is expanded; throws what the copy or a worker raised
+  void wait() {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return posted; });
+    for (auto& j : jobs) {
+      if (!j) continue;
+      try {
+        j->wait();
+      } catch (const std::exception& e) {
+        if (error.empty()) error = e.what();
+      }
+      j.reset();
+    }
+    TFA_CHECK(error.empty(), "packed output expansion failed: ", error);
+  }
+
+  std::mutex mu;
+  std::condition_variable cv;
+  bool posted = false;
+  std::string error;
+  std::vector<std::shared_ptr<unpack::Job>> jobs;
+};
+
+namespace {
+
+class PackLander {
+ public:
+  static PackLander& get() {
+    std::lock_guard<std::mutex> lk(inst_mu());
+    if (!inst()) inst().reset(new PackLander());
+    return *inst();
+  }
+  static void shutdown() {
+    std::unique_ptr<PackLander> p;
+    {
+      std::lock_guard<std::mutex> lk(inst_mu());
+      p = std::move(inst());
+    }
+    p.reset();
+  }
+  void submit(std::shared_ptr<PackLanding> l) {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      q_.push_back(std::move(l));
+    }
+    cv_.notify_one();
+  }
+  ~PackLander() {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      stop_ = true;
+    }
+    cv_.notify_all();
+    thread_.join();
+  }
+
+ private:
+  PackLander() : thread_([this] { loop(); }) {}
+  static std::mutex& inst_mu() {
+    static std::mutex m;
+    return m;
+  }
+  static std::unique_ptr<PackLander>& inst() {
+    static std::unique_ptr<PackLander> p;
+    return p;
+  }
+  void loop() {
+    for (;;) {
+      std::shared_ptr<PackLanding> l;
+      {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return stop_ || !q_.empty(); });
+        if (q_.empty()) return;
+        l = std::move(q_.front());
+        q_.pop_front();
+      }
+      std::string err;
+      std::vector<std::shared_ptr<unpack::Job>> jobs;
+      const hipError_t e = hipEventSynchronize(l->ev);
+      if (e != hipSuccess) {
+        err = std::string("D2H of a packed chunk: ") + hipGetErrorString(e);
+      } else {
+        try {
+          for (auto& t : l->tasks) jobs.push_back(unpack::global_pool().post_unpack(t.packed, t.out, t.rows, t.wpr));
+        } catch (const std::exception& ex) {
+          err = ex.what();
+        }
+      }
+      {
+        std::lock_guard<std::mutex> lk(l->mu);
+        l->jobs = std::move(jobs);
+        l->error = err;
+        l->posted = true;
+      }
+      l->cv.notify_all();
+    }
+  }
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::deque<std::shared_ptr<PackLanding>> q_;
+  bool stop_ = false;
+  std::thread thread_;
+};
+
+std::atomic<int>& pack_outputs_state() {
+  static std::atomic<int> v([] {
+    const char* e = std::getenv("TFA_PACK_OUTPUTS");
+    if (!e) return 1;
+    std::string s(e);  // as config._env reads a bool
+    for (auto& c : s) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+    return (s == "1" || s == "true" || s == "yes" || s == "on") ? 1 : 0;
+  }());
+  return v;
+}
+
+// completion of a run_chunked(wait=false) call
+struct PipeHandle {
+  hipEvent_t done = nullptr;
+  std::vector<std::shared_ptr<PackLanding>> landings;
+};
+
+}  // namespace
+
+void set_pack_outputs(bool on) { pack_outputs_state().store(on ? 1 : 0); }
+void set_pack_dense_fraction(double t) { g_pack_dense_fraction.store(t > 0 ? t : kPackDenseFraction); }
+double pack_dense_fraction() { return g_pack_dense_fraction.load(); }
+bool pack_outputs() { return pack_outputs_state().load() != 0; }
+
+void shutdown_pack_runtime() {
+  PackLander::shutdown();
+  unpack::shutdown_pool();
+}
+
 void Program::drop_pipe(bool synced) {
   if (!pipe_) return;
   if (pipe_->device >= 0) {
@@ -2341,17 +2502,39 @@ void Program::drop_pipe(bool synced) {
       (void)hipStreamSynchronize(copy_stream(pipe_->device, 1));
       (void)hipDeviceSynchronize();  // the compute streams that read the ring
     }
+    // the expansions still read the staging slots (and the completion thread
+    // their events)
+    for (auto& l : pipe_->landing)
+      if (l) {
+        try {
+          l->wait();
+        } catch (const std::exception&) {  // reported to the call's own waiter
+        }
+      }
     for (hipEvent_t e : pipe_->ev_comp) (void)hipEventDestroy(e);
     for (hipEvent_t e : pipe_->ev_d2h) (void)hipEventDestroy(e);
+    for (hipEvent_t e : pipe_->ev_land) (void)hipEventDestroy(e);
   }
   pipe_.reset();
 }
 
 void pipeline_wait(int64_t handle) {
   if (!handle) return;
-  hipEvent_t e = reinterpret_cast<hipEvent_t>(handle);
-  HIP_OK(hipEventSynchronize(e));
-  HIP_OK(hipEventDestroy(e));
+  std::unique_ptr<PipeHandle> h(reinterpret_cast<PipeHandle*>(handle));
+  const hipError_t e = hipEventSynchronize(h->done);
+  (void)hipEventDestroy(h->done);
+  // every expansion ends before the caller may drop the outputs, also after
+  // a failure
+  std::string err;
+  for (auto& l : h->landings) {
+    try {
+      l->wait();
+    } catch (const std::exception& ex) {
+      if (err.empty()) err = ex.what();
+    }
+  }
+  HIP_OK(e);
+  TFA_CHECK(err.empty(), err);
 }
 
 int64_t Program::run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inputs,
@@ -2432,6 +2615,7 @@ int64_t Program::run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inp
         HIP_OK(hipEventCreateWithFlags(&pipe_->ev_d2h[d], hipEventDisableTiming));
       }
       pipe_->used.assign(depth, false);
+      pipe_->d2h_issued.assign(depth, true);
     }
   }
   Pipe& P = *pipe_;
@@ -2444,7 +2628,47 @@ int64_t Program::run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inp
     }
   std::vector<hipEvent_t> ev_h2d(depth);
   for (int d = 0; d < depth; ++d) HIP_OK(hipEventCreateWithFlags(&ev_h2d[d], hipEventDisableTiming));
-  int64_t h2d_bytes = 0, d2h_bytes = 0;
+  int64_t h2d_bytes = 0, d2h_bytes = 0, d2h_dense_bytes = 0;
+  // zero-word packing (see "packed D2H" above). Eligible: a fetch whose rows
+  // are whole 32-bit words. packing[j]: pack fetch j's next chunk;
+  // probe_only[j]: an earlier chunk of it was dense, so only this call's first
+  // chunk is packed, to see whether that still holds.
+  const size_t nf = fetches_.size();
+  if (pack_dense_.size() != nf) pack_dense_.assign(nf, 0);
+  std::vector<char> packing(nf, 0), probe_only(nf, 0);
+  std::vector<int64_t> fetch_wpr(nf, 0);
+  if (pack_outputs()) {
+    bool any = false;
+    for (size_t j = 0; j < nf; ++j) {
+      const at::Tensor& dst = seg_outputs[chunks[0].seg][j];
+      const int64_t rb = dst.numel() / std::max<int64_t>(dst.size(0), 1) * dst.element_size();
+      if (rb <= 0 || rb % 4 != 0) continue;
+      fetch_wpr[j] = rb / 4;
+      packing[j] = 1;
+      probe_only[j] = pack_dense_[j];
+      any = true;
+    }
+    if (any && P.packed.empty()) {
+      P.packed.assign(depth, std::vector<at::Tensor>(nf));
+      P.stage.assign(kPackStages, std::vector<at::Tensor>(nf));
+      P.landing.assign(kPackStages, nullptr);
+      P.ev_land.resize(kPackStages);
+      for (auto& e : P.ev_land) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      P.counts = empty_pinned({static_cast<int64_t>(depth * nf)}, at::kLong);
+    }
+    for (size_t j = 0; j < nf; ++j) {
+      if (!packing[j]) continue;
+      // sized for the ring's capacity with nothing dropped: no overflow case.
+      // Fresh pool blocks of the compute stream, taken before the fork below.
+      const int64_t need = static_cast<int64_t>(pack_layout(P.rows, fetch_wpr[j]).max_bytes);
+      if (!P.packed[0][j].defined()) {
+        for (int d = 0; d < depth; ++d) P.packed[d][j] = dev_empty({need}, at::kByte, dev, compute.stream());
+        for (int k = 0; k < kPackStages; ++k) P.stage[k][j] = empty_pinned({need}, at::kByte);
+      } else if (P.packed[0][j].numel() < need) {
+        packing[j] = 0;  // (a fetch whose row size changed under a live pipeline)
+      }
+    }
+  }
   // per-stage device time (hipEvent pairs bracketing each chunk's H2D, compute
   // and D2H on their streams; read once after the final synchronisation)
   const bool timed = stage_timers_enabled() && wait;
@@ -2467,6 +2691,90 @@ int64_t Program::run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inp
     HIP_OK(hipEventRecord(fork_ev, compute.stream()));
     HIP_OK(hipStreamWaitEvent(cstr[1], fork_ev, 0));
   }
+  // The D2H of a chunk with a packed fetch needs the packed size, which only
+  // the finished pack kernel knows: such a chunk's D2H is issued one chunk
+  // late, by this thread, after the next chunk is enqueued (`lagged`). Every
+  // enqueue stays on this thread.
+  struct PendingD2H {
+    bool active = false;
+    size_t ci = 0;
+    int slot = 0;
+    std::vector<at::Tensor> outs;
+    std::vector<char> packed;  // per fetch: packed into P.packed[slot][j]
+    bool any_packed = false;
+  };
+  std::vector<std::shared_ptr<PackLanding>> call_landings;
+  uint64_t* const counts = P.counts.defined() ? reinterpret_cast<uint64_t*>(P.counts.data_ptr()) : nullptr;
+  auto issue_d2h = [&](PendingD2H& pd) {
+    const Chunk& ch = chunks[pd.ci];
+    const int slot = pd.slot;
+    std::shared_ptr<PackLanding> landing;
+    int stage = -1;
+    if (pd.any_packed) {
+      // the packed sizes: the chunk's pack kernels and count copies are done
+      HIP_OK(hipEventSynchronize(P.ev_comp[slot]));
+      stage = static_cast<int>(P.stage_next++ % kPackStages);
+      // the staging slot is free once its last expansion finished
+      if (P.landing[stage]) {
+        std::shared_ptr<PackLanding> prev = std::move(P.landing[stage]);
+        prev->wait();
+      }
+      landing = std::make_shared<PackLanding>();
+      landing->ev = P.ev_land[stage];
+    }
+    HIP_OK(hipStreamWaitEvent(d2h.stream(), P.ev_comp[slot], 0));
+    stamp(pd.ci, 4, d2h.stream());
+    for (size_t j = 0; j < pd.outs.size(); ++j) {
+      at::Tensor o = pd.outs[j];
+      const at::Tensor& dst = seg_outputs[ch.seg][j];
+      int64_t row_bytes = dst.numel() / std::max<int64_t>(dst.size(0), 1) * dst.element_size();
+      char* dp = static_cast<char*>(dst.data_ptr()) + ch.start * row_bytes;
+      d2h_dense_bytes += ch.rows * row_bytes;
+      if (pd.packed[j]) {
+        const PackLayout L = pack_layout(ch.rows, fetch_wpr[j]);
+        const uint64_t total = counts[slot * nf + j];
+        TFA_CHECK(total <= static_cast<uint64_t>(ch.rows * fetch_wpr[j]), "fetch '", fetch_names_[j],
+                  "': packed ", total, " words of ", ch.rows * fetch_wpr[j]);
+        const size_t bytes = L.values_off + static_cast<size_t>(total) * 4;
+        HIP_OK(hipMemcpyAsync(P.stage[stage][j].data_ptr(), P.packed[slot][j].data_ptr(), bytes,
+                              hipMemcpyDeviceToHost, d2h.stream()));
+        d2h_bytes += static_cast<int64_t>(bytes);
+        landing->tasks.push_back({P.stage[stage][j].data_ptr(), dp, ch.rows, fetch_wpr[j]});
+        // policy: a chunk that packs to more than kPackDenseFraction of its
+        // dense size ends packing of this fetch for the rest of the call, and
+        // later calls pack their first chunk only; a sparse probe resumes it
+        const bool dense =
+            static_cast<double>(bytes) > g_pack_dense_fraction.load() * static_cast<double>(ch.rows * row_bytes);
+        if (dense) {
+          packing[j] = 0;
+          pack_dense_[j] = 1;
+        } else if (pack_dense_[j]) {
+          pack_dense_[j] = 0;
+          probe_only[j] = 0;
+          packing[j] = 1;
+        }
+        continue;
+      }
+      if (!o.is_cuda()) o = o.to(dev);  // constant fetch
+      if (ch.rows * row_bytes)
+        HIP_OK(hipMemcpyAsync(dp, o.data_ptr(), ch.rows * row_bytes, hipMemcpyDeviceToHost, d2h.stream()));
+      dev_record_stream(o, d2h.stream());
+      d2h_bytes += ch.rows * row_bytes;
+    }
+    stamp(pd.ci, 5, d2h.stream());
+    HIP_OK(hipEventRecord(P.ev_d2h[slot], d2h.stream()));
+    P.d2h_issued[slot] = true;
+    if (landing) {
+      HIP_OK(hipEventRecord(landing->ev, d2h.stream()));
+      P.landing[stage] = landing;
+      call_landings.push_back(landing);
+      PackLander::get().submit(landing);
+      stats_.chunks_packed++;
+    }
+    pd.outs.clear();
+    pd.active = false;
+  };
+  PendingD2H lagged;
   for (size_t ci = 0; ci < chunks.size(); ++ci) {
     const hipStream_t cs = cstr[ci % ncomp];
     const Chunk& ch = chunks[ci];
@@ -2474,9 +2782,13 @@ int64_t Program::run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inp
     // H2D: wait until the compute (and any D2H of outputs aliasing the ring)
     // of the chunk that last used this slot finished (maybe in an earlier call)
     if (P.used[slot]) {
+      // (a ring of at least two slots with the D2H at most one chunk late:
+      // the slot's last D2H is queued, so its event is the current one)
+      TFA_CHECK(P.d2h_issued[slot], "run_chunked: slot ", slot, " reused before its D2H was issued");
       HIP_OK(hipStreamWaitEvent(h2d.stream(), P.ev_comp[slot], 0));
       HIP_OK(hipStreamWaitEvent(h2d.stream(), P.ev_d2h[slot], 0));
     }
+    P.d2h_issued[slot] = false;
     std::vector<at::Tensor> dev_in;
     stamp(ci, 0, h2d.stream());
     for (size_t i = 0; i < nin; ++i) {
@@ -2501,28 +2813,47 @@ int64_t Program::run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inp
       outs = execute(*p, dev_in, cs);
     }
     stamp(ci, 3, cs);
-    HIP_OK(hipEventRecord(P.ev_comp[slot], cs));
-    // D2H
-    HIP_OK(hipStreamWaitEvent(d2h.stream(), P.ev_comp[slot], 0));
-    stamp(ci, 4, d2h.stream());
+    PendingD2H pd;
+    pd.active = true;
+    pd.ci = ci;
+    pd.slot = slot;
+    pd.packed.assign(nf, 0);
     for (size_t j = 0; j < outs.size(); ++j) {
-      at::Tensor o = outs[j];
+      const at::Tensor& o = outs[j];
       const at::Tensor& dst = seg_outputs[ch.seg][j];
       int64_t row_bytes = dst.numel() / std::max<int64_t>(dst.size(0), 1) * dst.element_size();
       TFA_CHECK(o.size(0) == ch.rows && o.numel() * o.element_size() == ch.rows * row_bytes,
                 "fetch '", fetch_names_[j], "' produced ", o.size(0), " rows for a chunk of ", ch.rows);
-      if (!o.is_cuda()) o = o.to(dev);  // constant fetch
-      char* dp = static_cast<char*>(dst.data_ptr()) + ch.start * row_bytes;
-      if (ch.rows * row_bytes)
-        HIP_OK(hipMemcpyAsync(dp, o.data_ptr(), ch.rows * row_bytes, hipMemcpyDeviceToHost, d2h.stream()));
-      dev_record_stream(o, d2h.stream());
-      d2h_bytes += ch.rows * row_bytes;
+      if (!packing[j] || ch.rows == 0 || row_bytes != 4 * fetch_wpr[j]) continue;
+      // host constants and outputs that alias the input ring stay dense
+      bool plain = o.is_cuda() && o.is_contiguous();
+      for (size_t i = 0; plain && i < nin; ++i) {
+        const char* r0 = static_cast<const char*>(P.ring[slot][i].data_ptr());
+        const char* op = static_cast<const char*>(o.data_ptr());
+        if (op >= r0 && op < r0 + P.ring[slot][i].numel() * P.ring[slot][i].element_size()) plain = false;
+      }
+      if (!plain) continue;
+      if (!pd.any_packed && P.used[slot])  // the D2H that last read this slot's packed buffers
+        HIP_OK(hipStreamWaitEvent(cs, P.ev_d2h[slot], 0));
+      k::pack_words(o.data_ptr(), ch.rows, fetch_wpr[j], P.packed[slot][j].data_ptr(), cs);
+      HIP_OK(hipMemcpyAsync(counts + slot * nf + j, P.packed[slot][j].data_ptr(), 8, hipMemcpyDeviceToHost, cs));
+      pd.packed[j] = 1;
+      pd.any_packed = true;
+      if (probe_only[j]) packing[j] = 0;
     }
-    stamp(ci, 5, d2h.stream());
-    HIP_OK(hipEventRecord(P.ev_d2h[slot], d2h.stream()));
+    pd.outs = std::move(outs);
+    HIP_OK(hipEventRecord(P.ev_comp[slot], cs));
     P.used[slot] = true;
     stats_.chunks++;
+    // D2H: of the chunk before this one if that waits for its packed sizes,
+    // then of this one unless it has to wait for its own
+    if (lagged.active) issue_d2h(lagged);
+    if (pd.any_packed)
+      lagged = std::move(pd);
+    else
+      issue_d2h(pd);
   }
+  if (lagged.active) issue_d2h(lagged);
   if (ncomp > 1) {  // join: later work on the caller's stream follows every chunk
     HIP_OK(hipEventRecord(fork_ev, cstr[1]));
     HIP_OK(hipStreamWaitEvent(compute.stream(), fork_ev, 0));
@@ -2533,16 +2864,28 @@ int64_t Program::run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inp
     HIP_OK(hipStreamSynchronize(h2d.stream()));
     HIP_OK(hipStreamSynchronize(compute.stream()));
     HIP_OK(hipStreamSynchronize(d2h.stream()));
+    // ... and the packed chunks are expanded (all of them are waited for
+    // before the first failure is reported: the outputs are the caller's)
+    std::string err;
+    for (auto& l : call_landings) {
+      try {
+        l->wait();
+      } catch (const std::exception& ex) {
+        if (err.empty()) err = ex.what();
+      }
+    }
     // drained: the ring goes back to the pool (only a deferred sequence of
     // calls keeps it, to continue the slot rotation)
     drop_pipe(true);
+    TFA_CHECK(err.empty(), err);
   } else {
     // completion of this call = its last D2H (which waited for the last
-    // compute, which waited for the last H2D)
-    hipEvent_t done;
-    HIP_OK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-    HIP_OK(hipEventRecord(done, d2h.stream()));
-    handle = reinterpret_cast<int64_t>(done);
+    // compute, which waited for the last H2D) and its expansions
+    auto h = std::make_unique<PipeHandle>();
+    HIP_OK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(h->done, d2h.stream()));
+    h->landings = std::move(call_landings);
+    handle = reinterpret_cast<int64_t>(h.release());
   }
   // ev_h2d: compute already waits on them; destroying a recorded event is safe
   for (int d = 0; d < depth; ++d) hipEventDestroy(ev_h2d[d]);
@@ -2558,6 +2901,7 @@ int64_t Program::run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inp
   stats_.runs++;
   stats_.h2d_bytes += h2d_bytes;
   stats_.d2h_bytes += d2h_bytes;
+  stats_.d2h_dense_bytes += d2h_dense_bytes;
   stats_.wall_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
   stats_.h2d_ms += stage_ms[0];
   stats_.compute_ms += stage_ms[1];

@@ -35,14 +35,18 @@ struct ExecStats {
   int64_t plans_built = 0;
   int64_t plans_adopted = 0;  // plans taken over from a structurally equal program
   int64_t h2d_bytes = 0;
-  int64_t d2h_bytes = 0;
+  int64_t d2h_bytes = 0;        // bytes the D2H copies moved (packed fetches: their packed size)
+  int64_t d2h_dense_bytes = 0;  // bytes of the outputs those copies delivered
   int64_t chunks = 0;
+  int64_t chunks_packed = 0;    // run_chunked chunks with at least one fetch packed before its D2H
   double h2d_ms = 0, compute_ms = 0, d2h_ms = 0, wall_ms = 0;
   double plan_ms = 0;     // host time building plans (inference, fusion, kernel choice)
   double exec_ms = 0;     // host time issuing a plan's steps (launch overhead on a GPU)
   int64_t graphs_captured = 0, graph_replays = 0, graph_failures = 0, graphs_declined = 0;
   int64_t graph_busy = 0;  // pointer-keyed replays that copied their outputs out (the caller held the aliases)
 };
+
+struct PackLanding;  // one packed chunk between its D2H and the end of its expansion (executor.cpp)
 
 class Program {
  public:
@@ -95,9 +99,16 @@ class Program {
   // rotation of the previous one, so its first H2D waits only for the compute
   // of the chunk that last used that slot, not for the whole previous call.
   // wait = false: return as soon as every copy and kernel is enqueued (no
-  // synchronisation); the result is an event handle that completes when the
-  // last D2H has landed (pipeline_wait). The caller keeps seg_inputs and
-  // seg_outputs alive until then. wait = true: returns 0 after the drain.
+  // stream synchronisation); the result is a completion handle for
+  // pipeline_wait, which returns when the last D2H has landed and every
+  // packed chunk is expanded. The caller keeps seg_inputs and seg_outputs
+  // alive until then. wait = true: returns 0 after the drain.
+  //
+  // Fetches whose rows are whole 32-bit words cross PCIe packed (see "packed
+  // D2H" in executor.cpp) unless pack_outputs() is off: the D2H of such a
+  // chunk is issued one chunk late, when its packed size is known, and host
+  // threads expand it into seg_outputs. A fetch that packs to more than
+  // pack_dense_fraction() of its size goes back to plain copies.
   int64_t run_chunked(const std::vector<std::vector<at::Tensor>>& seg_inputs,
                       const std::vector<std::vector<at::Tensor>>& seg_outputs, int64_t chunk_rows,
                       int device, int depth, bool wait = true);
@@ -173,9 +184,23 @@ class Program {
     std::vector<hipEvent_t> ev_comp, ev_d2h;   // per slot: last compute / D2H that used it
     std::vector<bool> used;
     int64_t next = 0;                          // chunk counter (slot = next % depth)
+    // zero-word packing of sparse fetches (run_chunked): per ring slot and
+    // fetch a packed device buffer (undefined tensor: fetch not eligible) and
+    // a pinned 8-byte value count; kPackStages pinned staging slots per fetch
+    // that a packed D2H lands in and the unpack pool expands from
+    std::vector<bool> d2h_issued;              // per slot: its last chunk's D2H is queued (ev_d2h is current)
+    std::vector<std::vector<at::Tensor>> packed;  // [slot][fetch]
+    at::Tensor counts;                            // pinned uint64 [slot][fetch]
+    std::vector<std::vector<at::Tensor>> stage;   // [stage][fetch]
+    std::vector<hipEvent_t> ev_land;              // per stage: its last packed D2H landed
+    std::vector<std::shared_ptr<PackLanding>> landing;  // per stage: its last expansion
+    int64_t stage_next = 0;
   };
   std::mutex pipe_mu_;
   std::unique_ptr<Pipe> pipe_;
+  // per fetch: an earlier chunk packed to more than kPackDenseFraction of its
+  // dense size, so calls pack only their first chunk (a re-probe)
+  std::vector<char> pack_dense_;
   // caller holds pipe_mu_: free ring and events (draining the streams first
   // unless `synced`)
   void drop_pipe(bool synced);
@@ -192,8 +217,19 @@ void set_step_timing(bool on);
 bool step_timing();
 std::vector<StepTiming> read_step_timing();
 
-// waits for (and releases) an event handle returned by run_chunked(wait=false)
+// waits for (and releases) a completion handle returned by
+// run_chunked(wait=false): its last D2H and the expansions of its packed chunks
 void pipeline_wait(int64_t handle);
+// zero-word packing of run_chunked outputs (config.pack_outputs,
+// TFA_PACK_OUTPUTS; default on)
+void set_pack_outputs(bool on);
+bool pack_outputs();
+// the packed / dense size ratio above which a fetch goes back to plain
+// copies (t <= 0: the built-in value); for the threshold sweep
+void set_pack_dense_fraction(double t);
+double pack_dense_fraction();
+// joins the completion thread and the unpack pool (module teardown)
+void shutdown_pack_runtime();
 
 // pinned host memory (hipHostMalloc, exact size; freed with hipHostFree)
 at::Tensor empty_pinned(const std::vector<int64_t>& sizes, at::ScalarType dt);

@@ -37,6 +37,12 @@ class Config:
     min_pipeline_chunks: int = dataclasses.field(default_factory=lambda: _env("TFA_MIN_PIPELINE_CHUNKS", 16, int))
     # ring depth of the copy/compute pipeline
     pipeline_depth: int = dataclasses.field(default_factory=lambda: _env("TFA_PIPELINE_DEPTH", 3, int))
+    # pipelined outputs whose rows are whole 32-bit words cross PCIe packed
+    # (a 1-bit-per-word mask plus the non-zero words, kernels/pack_words.hip)
+    # and are expanded by host threads (TFA_UNPACK_THREADS); a fetch that
+    # turns out dense goes back to plain copies by itself. The native runtime
+    # reads the same variable, so the two agree without a call.
+    pack_outputs: bool = dataclasses.field(default_factory=lambda: _env("TFA_PACK_OUTPUTS", True, bool))
     # partitions smaller than this run in one shot (no chunking)
     min_chunked_rows: int = dataclasses.field(default_factory=lambda: _env("TFA_MIN_CHUNKED_ROWS", 65536, int))
     # ... or at least this many input bytes (a partition of 2048 images is 1.2 GB:
@@ -154,6 +160,9 @@ def set_config(**kw):
         os.environ["TFA_DEBUG_SYNC"] = "1" if kw["debug_sync"] else "0"
         from ._native import _C
         _C.set_debug_sync(bool(kw["debug_sync"]))  # read by the executor on every launch
+    if "pack_outputs" in kw:
+        from ._native import _C
+        _C.set_pack_outputs(bool(kw["pack_outputs"]))
     if "precision" in kw:
         apply_precision()
     if "pool_conv_fusion" in kw:
