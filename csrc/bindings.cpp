@@ -921,6 +921,48 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("idx"), py::arg("cols"),
      "output row j of every device column = its row idx[j] (idx: device int64 [n_out], entries in [0, rows), "
      "repeats allowed), all columns in one launch");
+  // DataFrame.dropDuplicates / distinct on device-resident partitions (kernels/unique.hip)
+  m.def("unique_tile_rows", [] { return k::unique_tile_rows(); }, "positions per tile of unique_rows");
+  m.def("unique_rows", [](const at::Tensor& words0, std::optional<at::Tensor> perm0) {
+    if (!words0.is_cuda()) throw py::value_error("unique_rows: the words must be a device tensor");
+    if (words0.scalar_type() != at::kLong)
+      throw py::type_error(str_cat("unique_rows: the words must be int64, got ", c10::toString(words0.scalar_type())));
+    if (words0.dim() != 2) throw py::value_error(str_cat("unique_rows: words [W, n] expected, got ", words0.dim(), "-D"));
+    const int64_t W = words0.size(0), n = words0.size(1);
+    if (W < 1 || W > k::kMaxSortKeys)
+      throw py::value_error(str_cat("unique_rows: 1..", k::kMaxSortKeys, " words per row, got ", W));
+    if (!words0.is_contiguous()) throw py::value_error("unique_rows: the words must be contiguous");
+    const int64_t* pp = nullptr;
+    at::Tensor perm;
+    if (perm0.has_value()) {
+      if (perm0->scalar_type() != at::kLong)
+        throw py::type_error(str_cat("unique_rows: the order must be int64, got ", c10::toString(perm0->scalar_type())));
+      if (!perm0->is_cuda() || perm0->device() != words0.device())
+        throw py::value_error("unique_rows: the order must be a device tensor on the words' device");
+      if (perm0->dim() != 1 || perm0->size(0) != n)
+        throw py::value_error(str_cat("unique_rows: the order must hold one entry per row ([", n, "]), got ",
+                                      perm0->dim(), "-D with ", perm0->numel(), " entries"));
+      perm = perm0->contiguous();
+      pp = perm.data_ptr<int64_t>();
+    }
+    c10::hip::HIPGuard guard(words0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(words0.device().index()).stream();
+    if (n == 0) return pool_empty({0}, words0.options());
+    const size_t wsb = k::unique_workspace_bytes(n);
+    // (int64 elements: the workspace starts with 64-bit offsets)
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, words0.options());
+    int64_t total = 0;
+    {
+      py::gil_scoped_release nogil;
+      total = k::unique_plan(words0.data_ptr<int64_t>(), static_cast<int>(W), n, pp, ws.data_ptr(), ws.numel() * 8, s);
+    }
+    at::Tensor kept = pool_empty({total}, words0.options());
+    k::unique_write(pp, n, total, ws.data_ptr(), kept.data_ptr<int64_t>(), s);
+    return kept;
+  }, py::arg("words"), py::arg("perm") = py::none(),
+     "words [W, n] (sort_encode) in the stable order perm (sort_argsort; None: in order already) -> int64 [m]: "
+     "perm[i] of every position i that starts a run of equal word tuples, in order (source row indices for "
+     "take_rows); one stream synchronisation reads the count");
   // DataFrame.join on device-resident partitions (kernels/join.hip)
   m.def("join_tile_rows", [] { return k::join_tile_rows(); }, "output rows per block of join_expand");
   m.def("join_gather_words", [](const at::Tensor& words0, const at::Tensor& perm0) {

@@ -266,6 +266,11 @@ size_t compact_workspace_bytes(int64_t n) {
   return static_cast<size_t>(8 + 8 * t + 4 * t);
 }
 
+void compact_scan_counts(const int32_t* counts, int64_t ntiles, int64_t* offs, int64_t* total, hipStream_t s) {
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kScanT), 0, s, counts, ntiles, offs, total);
+  TFA_LAUNCH_CHECK("compact_scan_kernel");
+}
+
 int64_t compact_plan(const uint8_t* mask, int64_t n, void* ws, size_t ws_size, hipStream_t s) {
   if (n <= 0) return 0;
   const int64_t ntiles = compact_tiles(n);
@@ -276,8 +281,7 @@ int64_t compact_plan(const uint8_t* mask, int64_t n, void* ws, size_t ws_size, h
   int32_t* counts = reinterpret_cast<int32_t*>(offs + ntiles);
   hipLaunchKernelGGL(compact_plan_kernel, dim3((unsigned)ntiles), dim3(kCT), 0, s, mask, n, counts);
   TFA_LAUNCH_CHECK("compact_plan_kernel");
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kScanT), 0, s, counts, ntiles, offs, total);
-  TFA_LAUNCH_CHECK("compact_scan_kernel");
+  compact_scan_counts(counts, ntiles, offs, total, s);
   int64_t got = 0;
   TFA_CHECK(hipMemcpyAsync(&got, total, sizeof(got), hipMemcpyDeviceToHost, s) == hipSuccess,
             "compact: D2H of the kept count failed");

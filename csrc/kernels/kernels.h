@@ -196,6 +196,9 @@ size_t compact_workspace_bytes(int64_t n);
 int64_t compact_plan(const uint8_t* mask, int64_t n, void* workspace, size_t workspace_size, hipStream_t s);
 void compact_gather(const PackCols& src, const PackCols& dst, const uint8_t* mask, int64_t n, int64_t total,
                     const void* workspace, int64_t* index, hipStream_t s);
+// the single-block scan under compact_plan, for other plan / write kernels:
+// offs[t] = sum of counts[0 .. t), *total = the sum of all (device pointers)
+void compact_scan_counts(const int32_t* counts, int64_t ntiles, int64_t* offs, int64_t* total, hipStream_t s);
 
 // ------------------------------------------------------------ zero-word packing (pack_words.hip)
 // Packs a contiguous device buffer of rows x wpr 32-bit words into `packed`
@@ -243,6 +246,22 @@ void take_rows(const PackCols& src, const PackCols& dst, const int64_t* idx, int
 // ([S][W], row-major), lexicographically as unsigned words
 void sort_bounds(const int64_t* words, int W, int64_t n, const int64_t* perm, const int64_t* splitters, int64_t S,
                  int64_t* out, hipStream_t s);
+
+// ------------------------------------------------------------ distinct rows (unique.hip)
+// DataFrame.dropDuplicates / distinct: the first row of every run of equal
+// word tuples in a sorted order. words [W][n] are sort_encode's, perm [n] is
+// sort_argsort's stable order (null: the rows are in order already). Position
+// i is a head when i == 0 or any word of row perm[i] differs from that word of
+// row perm[i - 1]. unique_plan writes the head bits and the tile offsets into
+// the workspace and returns the number of heads (synchronises the stream once
+// to read it, like compact_plan); unique_write then stores perm[i] of every
+// head, in order, into kept [total]. perm values must lie in [0, n).
+int unique_tile_rows();
+size_t unique_workspace_bytes(int64_t n);
+int64_t unique_plan(const int64_t* words, int W, int64_t n, const int64_t* perm, void* workspace,
+                    size_t workspace_size, hipStream_t s);
+void unique_write(const int64_t* perm, int64_t n, int64_t total, const void* workspace, int64_t* kept,
+                  hipStream_t s);
 
 // ------------------------------------------------------------ join (join.hip)
 // DataFrame.join: an equi-join of two frames on key tuples. Keys are the words

@@ -136,6 +136,57 @@ class _Derived(_Source):
             yield pid, res[pid]
 
 
+class _Union(_Source):
+    """The partitions of two parents side by side (DataFrame.union): the left
+    parent's partition q stays q, the right parent's partition p becomes
+    n1 + p, its columns under the left parent's names (`relabel`: a new Block
+    over the same column objects; nothing is copied). Ownership is
+    p % world: when world == 1 or n1 % world == 0 the right parent's blocks
+    stay where they are and the source streams; otherwise one exchange moves
+    each of them whole to the owner of n1 + p (collective: not streamable)."""
+
+    def __init__(self, left: "DataFrame", right: "DataFrame", relabel: Callable[[Block], Block],
+                 keep_on_device: bool = False):
+        self._left = left
+        self._right = right
+        self._relabel = relabel
+        self._keep_on_device = keep_on_device  # the right parent is device-resident: what the exchange staged goes back
+
+    @property
+    def streamable(self) -> bool:
+        w = dist.world_size()
+        return w == 1 or self._left.num_partitions % w == 0
+
+    def compute(self):
+        n1, n2 = self._left.num_partitions, self._right.num_partitions
+        if self.streamable:
+            res = dict(self._left._blocks())
+            res.update({n1 + p: self._relabel(b) for p, b in self._right._blocks().items()})
+            return res
+
+        def exchange():
+            from .. import engine
+            from ..parallel import frame_comm
+            res = dict(self._left._blocks())
+            right = {p: self._relabel(b) for p, b in self._right._blocks().items()}
+            counts = frame_comm.partition_rows({p: b.nrows for p, b in right.items()}, n2)
+            pieces = {p: ([(n1 + p, 0, counts[p])] if counts[p] else []) for p in range(n2)}
+            schema = self._left.schema
+            got = frame_comm.exchange_pieces(right, schema.names, schema, n1 + n2, pieces)
+            got = {q: b for q, b in got.items() if q >= n1}
+            if self._keep_on_device and engine.gpu_available():
+                got = {q: b.to(engine.compute_device()) for q, b in got.items()}
+            res.update(got)
+            return res
+        return dist.agreed("union", exchange)
+
+    def iterate(self):
+        n1 = self._left.num_partitions
+        yield from self._left._iter_blocks()
+        for p, b in self._right._iter_blocks():
+            yield n1 + p, self._relabel(b)
+
+
 _MAX_GROUP_PARTITIONS = 16  # bound for columns whose size is only estimated
 
 
@@ -244,6 +295,8 @@ class DataFrame:
             for p in dist.local_partitions(src._n):
                 yield p, src._fn(p)
         elif isinstance(src, _Derived) and src.streamable:
+            yield from src.iterate()
+        elif isinstance(src, _Union) and src.streamable:
             yield from src.iterate()
         else:
             blocks = self._blocks()
@@ -598,6 +651,72 @@ class DataFrame:
         partitions are joined on the device (kernels/join.hip)."""
         from .join import _join_frame
         return _join_frame(self, other, on, how)
+
+    def union(self, other: "DataFrame") -> "DataFrame":
+        """The rows of this frame, then the rows of `other`, columns resolved
+        by POSITION (as in Spark): names and metadata are this frame's, an
+        analyzed lead dimension becomes unknown and the cell shapes must
+        agree. Column types must be equal: there is no implicit widening
+        (`.cast()` one side first). The result has `num_partitions +
+        other.num_partitions` partitions, this frame's first, so
+        `a.union(b).dropDuplicates(["id"])` prefers `a`'s rows. Lazy; blocks
+        are never copied and device-resident blocks stay on the device.
+        Across ranks, `other`'s partitions move to their new owners in one
+        exchange unless this frame's partition count divides by the world
+        size."""
+        from .setops import _union_frame
+        return _union_frame(self, other, False, "union")
+
+    unionAll = union  # noqa: N815
+    union_all = union
+
+    def unionByName(self, other: "DataFrame") -> "DataFrame":  # noqa: N802
+        """`union` with `other`'s columns resolved by NAME: they are reordered
+        to this frame's order; a missing or an extra name is a ValueError."""
+        from .setops import _union_frame
+        return _union_frame(self, other, True, "unionByName")
+
+    union_by_name = unionByName
+
+    def dropDuplicates(self, subset=None) -> "DataFrame":  # noqa: N802
+        """One row per distinct tuple of the key columns `subset` (a list of
+        names; None: every column). Keys follow `orderBy`'s rules (up to 8
+        numeric scalar columns; NaN equals NaN, -0.0 equals 0.0); the other
+        columns may be of any kind and follow the kept rows.
+
+        Defined differences from Spark: the kept row is the FIRST occurrence
+        in input order (partition order, then row order; Spark keeps an
+        arbitrary one), and the result is in the order of `orderBy(*keys)`,
+        ascending, in the same number of partitions. Neither the kept rows
+        nor their order and placement depend on the number of ranks.
+        Sort-based: every partition is sorted and reduced to its distinct
+        rows BEFORE the exchange of `orderBy` (at most the locally distinct
+        rows travel), what arrives is sorted and reduced again.
+        Device-resident partitions use the sort kernels and kernels/unique.hip."""
+        from .setops import _distinct_frame
+        return _distinct_frame(self, subset, "dropDuplicates")
+
+    drop_duplicates = dropDuplicates
+
+    def distinct(self) -> "DataFrame":
+        """`dropDuplicates()` over every column."""
+        from .setops import _distinct_frame
+        return _distinct_frame(self, None, "distinct")
+
+    def intersect(self, other: "DataFrame") -> "DataFrame":
+        """The distinct rows of this frame that `other` holds too (columns by
+        position, types as in `union`): `distinct()`, then a left-semi
+        broadcast join on all columns, so the result keeps `distinct`'s order
+        and `join`'s limits (`other` is gathered on every rank; at most 8
+        columns, all numeric scalars)."""
+        from .setops import _semi_frame
+        return _semi_frame(self, other, "left_semi", "intersect")
+
+    def subtract(self, other: "DataFrame") -> "DataFrame":
+        """The distinct rows of this frame that `other` does not hold (see
+        `intersect`; a left-anti join)."""
+        from .setops import _semi_frame
+        return _semi_frame(self, other, "left_anti", "subtract")
 
     def describe(self, *cols) -> "DataFrame":
         """count, mean, stddev, min and max of the named columns, or of every
@@ -1048,6 +1167,30 @@ def _order_blocks(blocks: Dict[int, Block], names: Sequence[str], schema: Struct
     return {q: _sort_block(b, keys, desc, stats)[0] for q, b in got.items()}
 
 
+def _check_sort_key(f: StructField, shown: str, what: str) -> None:
+    """The typed refusals of a key column of orderBy and of the operators built
+    on its order (dropDuplicates, distinct): a numeric scalar per row."""
+    from .. import core
+    if isinstance(f.dataType, (StringType, BinaryType)):
+        raise core.InvalidTypeException(
+            f"{what}: '{shown}' is a {type(f.dataType).__name__[:-4].lower()} column; string and binary "
+            f"columns are not supported as sort keys yet")
+    stf = ColumnInformation(f).stf
+    if stf is None:
+        raise core.InvalidTypeException(f"{what}: the type of '{shown}' ({f.dataType}) is not supported as a "
+                                        f"sort key")
+    if stf.tf_dtype in (D.DT_HALF, D.DT_BFLOAT16):
+        raise core.InvalidTypeException(f"{what}: '{shown}' is {D.dtype_name(stf.tf_dtype)}; half and bfloat16 "
+                                        f"columns are not supported as sort keys yet (cast to float)")
+    if stf.tf_dtype not in _SORT_KEY_DTYPES:
+        raise core.InvalidTypeException(f"{what}: '{shown}' is {D.dtype_name(stf.tf_dtype)}, which is not "
+                                        f"supported as a sort key")
+    if stf.shape.num_dims != 1:
+        raise core.InvalidDimensionException(
+            f"{what}: the key '{shown}' holds a cell of rank {max(stf.shape.num_dims - 1, 0)} per row, not a "
+            f"scalar; reduce the cell first (.sum(), .max(), ...)")
+
+
 def _sort_frame(df: DataFrame, cols: Sequence[Any], ascending, global_order: bool, what: str) -> DataFrame:
     """The lazy frame of orderBy / sortWithinPartitions: everything is
     validated here (typed errors); computed keys become temporary columns
@@ -1091,26 +1234,7 @@ def _sort_frame(df: DataFrame, cols: Sequence[Any], ascending, global_order: boo
             extra.append(Column(it._expr, f"tfa_sort_key_{k}"))
     base = df._select_columns(list(df.columns) + extra) if extra else df
     for k, it in zip(keys, items):
-        shown = it if isinstance(it, str) else it.output_name
-        f = base.schema[k]
-        if isinstance(f.dataType, (StringType, BinaryType)):
-            raise core.InvalidTypeException(
-                f"{what}: '{shown}' is a {type(f.dataType).__name__[:-4].lower()} column; string and binary "
-                f"columns are not supported as sort keys yet")
-        stf = ColumnInformation(f).stf
-        if stf is None:
-            raise core.InvalidTypeException(f"{what}: the type of '{shown}' ({f.dataType}) is not supported as a "
-                                            f"sort key")
-        if stf.tf_dtype in (D.DT_HALF, D.DT_BFLOAT16):
-            raise core.InvalidTypeException(f"{what}: '{shown}' is {D.dtype_name(stf.tf_dtype)}; half and bfloat16 "
-                                            f"columns are not supported as sort keys yet (cast to float)")
-        if stf.tf_dtype not in _SORT_KEY_DTYPES:
-            raise core.InvalidTypeException(f"{what}: '{shown}' is {D.dtype_name(stf.tf_dtype)}, which is not "
-                                            f"supported as a sort key")
-        if stf.shape.num_dims != 1:
-            raise core.InvalidDimensionException(
-                f"{what}: the key '{shown}' holds a cell of rank {max(stf.shape.num_dims - 1, 0)} per row, not a "
-                f"scalar; reduce the cell first (.sum(), .max(), ...)")
+        _check_sort_key(base.schema[k], it if isinstance(it, str) else it.output_name, what)
     names = base.columns
     schema = base.schema
     nparts = df.num_partitions
