@@ -1523,6 +1523,118 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "frames[o] (rows, range, whole), read from channel chans[o]. carry[c] / carry_rows: the fold of the first "
      "group's pieces in earlier partitions, applied on the left when has_carry; total[c] / total_rows: the whole-"
      "group values of the last group when it runs on into a later partition (has_total)");
+  // DataFrame.sample / randomSplit / sampleBy, F.rand / F.randn (kernels/random.hip)
+  m.def("random_tile_rows", [] { return k::random_tile_rows(); }, "rows per block of the random_* kernels");
+  // options of a [n] output on `device` (-1: the current one), after the checks every draw shares
+  auto random_options = [](const char* what, int64_t row0, int64_t n, int64_t device) {
+    if (n < 0) throw py::value_error(str_cat(what, ": a row count >= 0 is expected, got ", n));
+    if (row0 < 0) throw py::value_error(str_cat(what, ": a global row index >= 0 is expected, got ", row0));
+    if (row0 > std::numeric_limits<int64_t>::max() - n)
+      throw py::value_error(str_cat(what, ": row0 + n passes 2^63 (", row0, " + ", n, ")"));
+    const int ndev = static_cast<int>(c10::hip::device_count());
+    if (ndev < 1) throw py::value_error(str_cat(what, ": no GPU is available"));
+    if (device < -1 || device >= ndev)
+      throw py::value_error(str_cat(what, ": device ", device, " does not exist (", ndev, " devices)"));
+    const auto idx = static_cast<c10::DeviceIndex>(device < 0 ? c10::hip::current_device() : device);
+    return at::TensorOptions().device(at::Device(at::kCUDA, idx));
+  };
+  m.def("random_uniform", [random_options](uint64_t seed, int64_t row0, int64_t n, int64_t device) {
+    const auto opts = random_options("random_uniform", row0, n, device).dtype(at::kDouble);
+    c10::hip::HIPGuard guard(opts.device().index());
+    at::Tensor out = pool_empty({n}, opts);
+    k::random_uniform(seed, static_cast<uint64_t>(row0), n, out.data_ptr<double>(),
+                      c10::hip::getCurrentHIPStream(opts.device().index()).stream());
+    return out;
+  }, py::arg("seed"), py::arg("row0"), py::arg("n"), py::arg("device") = -1,
+     "float64 [n] on the device: u of the rows row0 .. row0 + n of the Philox4x32-10 stream of `seed` (an unsigned "
+     "64-bit key; counter (row low, row high, 0, 0)), u = (((w0 << 32) | w1) >> 11) * 2^-53 in [0, 1)");
+  m.def("random_normal", [random_options](uint64_t seed, int64_t row0, int64_t n, int64_t device) {
+    const auto opts = random_options("random_normal", row0, n, device).dtype(at::kDouble);
+    c10::hip::HIPGuard guard(opts.device().index());
+    at::Tensor out = pool_empty({n}, opts);
+    k::random_normal(seed, static_cast<uint64_t>(row0), n, out.data_ptr<double>(),
+                     c10::hip::getCurrentHIPStream(opts.device().index()).stream());
+    return out;
+  }, py::arg("seed"), py::arg("row0"), py::arg("n"), py::arg("device") = -1,
+     "float64 [n]: the first Box-Muller normal of every row (counter word 2 is 1): sqrt(-2 ln u1) * cospi(2 u2), u1 "
+     "from (w0, w1) in (0, 1], u2 from (w2, w3) in [0, 1)");
+  m.def("random_mask", [random_options](uint64_t seed, int64_t row0, int64_t n, double lo, double hi,
+                                        int64_t device) {
+    const auto opts = random_options("random_mask", row0, n, device).dtype(at::kByte);
+    if (std::isnan(lo) || std::isnan(hi))
+      throw py::value_error(str_cat("random_mask: the bounds must be numbers, got ", lo, " and ", hi));
+    c10::hip::HIPGuard guard(opts.device().index());
+    at::Tensor out = pool_empty({n}, opts);
+    k::random_mask(seed, static_cast<uint64_t>(row0), n, lo, hi, static_cast<uint8_t*>(out.data_ptr()),
+                   c10::hip::getCurrentHIPStream(opts.device().index()).stream());
+    return out;
+  }, py::arg("seed"), py::arg("row0"), py::arg("n"), py::arg("lo"), py::arg("hi"), py::arg("device") = -1,
+     "uint8 [n]: lo <= u < hi of every row's uniform draw (the byte mask compact_rows takes)");
+  m.def("random_mask_by", [random_options](uint64_t seed, int64_t row0, const at::Tensor& words,
+                                           const at::Tensor& table_words, const at::Tensor& table_fractions) {
+    if (!words.is_cuda() || words.scalar_type() != at::kLong || words.dim() != 2 || words.size(0) != 1 ||
+        !words.is_contiguous())
+      throw py::value_error("random_mask_by: contiguous device int64 words [1, n] (sort_encode of one key) expected");
+    const int64_t n = words.size(1);
+    if (!table_words.is_cuda() || table_words.device() != words.device() || table_words.scalar_type() != at::kLong ||
+        table_words.dim() != 1 || !table_words.is_contiguous())
+      throw py::value_error("random_mask_by: a contiguous int64 word table [S] on the words' device expected");
+    const int64_t S = table_words.size(0);
+    if (S < 1 || S > k::kMaxStrata)
+      throw py::value_error(str_cat("random_mask_by: 1..", k::kMaxStrata, " strata per call, got ", S));
+    if (!table_fractions.is_cuda() || table_fractions.device() != words.device() ||
+        table_fractions.scalar_type() != at::kDouble || table_fractions.dim() != 1 || table_fractions.size(0) != S ||
+        !table_fractions.is_contiguous())
+      throw py::value_error(str_cat("random_mask_by: a contiguous float64 fraction table [", S,
+                                    "] on the words' device expected"));
+    const auto opts = random_options("random_mask_by", row0, n, words.device().index()).dtype(at::kByte);
+    c10::hip::HIPGuard guard(words.device().index());
+    at::Tensor out = pool_empty({n}, opts);
+    k::random_mask_by(seed, static_cast<uint64_t>(row0), n, words.data_ptr<int64_t>(), table_words.data_ptr<int64_t>(),
+                      table_fractions.data_ptr<double>(), static_cast<int>(S), static_cast<uint8_t*>(out.data_ptr()),
+                      c10::hip::getCurrentHIPStream(words.device().index()).stream());
+    return out;
+  }, py::arg("seed"), py::arg("row0"), py::arg("words"), py::arg("table_words"), py::arg("table_fractions"),
+     "uint8 [n]: u < the fraction of the row's stratum. words [1, n]: sort_encode of the key column; table_words [S] "
+     "ascending (as unsigned words) and distinct, table_fractions [S]; a word the table does not hold gives 0. At "
+     "most 4096 strata (the table is staged in LDS)");
+  m.def("random_poisson", [random_options](uint64_t seed, int64_t row0, int64_t n, const at::Tensor& cdf) {
+    if (!cdf.is_cuda() || cdf.scalar_type() != at::kDouble || cdf.dim() != 1 || !cdf.is_contiguous())
+      throw py::value_error("random_poisson: a contiguous device float64 table [len] expected");
+    if (cdf.size(0) < 1 || cdf.size(0) > k::kMaxPoissonTable)
+      throw py::value_error(str_cat("random_poisson: a table of 1..", k::kMaxPoissonTable, " entries, got ",
+                                    cdf.size(0)));
+    const auto opts = random_options("random_poisson", row0, n, cdf.device().index()).dtype(at::kLong);
+    c10::hip::HIPGuard guard(cdf.device().index());
+    at::Tensor out = pool_empty({n}, opts);
+    k::random_poisson(seed, static_cast<uint64_t>(row0), n, cdf.data_ptr<double>(), static_cast<int>(cdf.size(0)),
+                      out.data_ptr<int64_t>(), c10::hip::getCurrentHIPStream(cdf.device().index()).stream());
+    return out;
+  }, py::arg("seed"), py::arg("row0"), py::arg("n"), py::arg("cdf"),
+     "int64 [n] on cdf's device: per row the number of entries of the non-decreasing table cdf [1..64] that are <= u "
+     "(counter word 2 is 2): a Poisson count when cdf is the distribution function");
+  m.def("random_expand", [](const at::Tensor& counts0) {
+    if (!counts0.is_cuda() || counts0.scalar_type() != at::kLong || counts0.dim() != 1)
+      throw py::value_error("random_expand: device int64 counts [n] expected");
+    const int64_t n = counts0.size(0);
+    c10::hip::HIPGuard guard(counts0.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(counts0.device().index()).stream();
+    at::Tensor counts = counts0.contiguous();
+    at::Tensor offs = pool_empty({n + 1}, counts.options());
+    int64_t total = 0;
+    {
+      const size_t wsb = k::join_scan_workspace_bytes(n);
+      at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, counts.options());
+      py::gil_scoped_release nogil;
+      total = k::join_scan(counts.data_ptr<int64_t>(), n, k::kMaxPoissonTable, offs.data_ptr<int64_t>(), ws.data_ptr(),
+                           static_cast<size_t>(ws.numel()) * 8, s);
+    }
+    at::Tensor idx = pool_empty({total}, counts.options());
+    k::random_expand(offs.data_ptr<int64_t>(), n, total, idx.data_ptr<int64_t>(), s);
+    return idx;
+  }, py::arg("counts"),
+     "random_poisson's counts [n] (each 0..64) -> int64 [sum]: row i counts[i] times, rows in order (the exclusive "
+     "scan of join_expand, the left indices only; feeds take_rows); one stream synchronisation reads the total");
   // native JPEG decode into one ragged (pinned) buffer (runtime/jpeg_decode.cpp)
   struct PyJpegBatch {
     std::vector<py::buffer_info> views;  // keep the cells' buffers exported while decoding

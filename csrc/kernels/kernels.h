@@ -465,6 +465,35 @@ struct WindowFinishSpec {
 // row (WHOLE; the total when the group runs on), decoded to the output column.
 void window_finish(const int64_t* fwd, const int64_t* rev, int64_t n, const WindowFinishSpec& spec, hipStream_t s);
 
+// ------------------------------------------------------------ random draws (random.hip)
+// DataFrame.sample / randomSplit / sampleBy, F.rand / F.randn. Row i of a call
+// draws from Philox4x32-10 with the key (seed low, seed high) and the counter
+// (row low, row high, purpose, 0), row = row0 + i (64-bit), purpose 0 uniform,
+// 1 normal, 2 poisson; the four words w0..w3 of one call serve one row:
+//   u  = (((w0 << 32) | w1) >> 11) * 2^-53                         (exact)
+//   z  = sqrt(-2 ln u1) * cospi(2 u2), u1 = (bits53(w0, w1) + 1) * 2^-53,
+//        u2 = bits53(w2, w3) * 2^-53
+// n == 0 launches nothing; outputs are [n], contiguous.
+constexpr int kMaxStrata = 4096;       // sampleBy table entries (64 KiB of LDS)
+constexpr int kMaxPoissonTable = 64;   // entries of a Poisson cdf table
+int random_tile_rows();  // rows per block
+void random_uniform(uint64_t seed, uint64_t row0, int64_t n, double* out, hipStream_t s);
+void random_normal(uint64_t seed, uint64_t row0, int64_t n, double* out, hipStream_t s);
+// mask[i] = (lo <= u_i && u_i < hi), one byte per row (compact_rows' mask)
+void random_mask(uint64_t seed, uint64_t row0, int64_t n, double lo, double hi, uint8_t* mask, hipStream_t s);
+// mask[i] = u_i < table_fractions[t] where table_words[t] == words[i], 0 when
+// no entry does. words [n] are sort_encode's (one key); table_words [strata]
+// ascending as unsigned words and distinct, 1 <= strata <= kMaxStrata
+void random_mask_by(uint64_t seed, uint64_t row0, int64_t n, const int64_t* words, const int64_t* table_words,
+                    const double* table_fractions, int strata, uint8_t* mask, hipStream_t s);
+// counts[i] = entries of cdf [len] (non-decreasing, 1 <= len <= kMaxPoissonTable)
+// that are <= u_i, u drawn under purpose 2
+void random_poisson(uint64_t seed, uint64_t row0, int64_t n, const double* cdf, int len, int64_t* counts,
+                    hipStream_t s);
+// offs [n + 1] = the exclusive scan of counts (join_scan; offs[n] == total):
+// idx [total] holds row i offs[i + 1] - offs[i] times, rows in order
+void random_expand(const int64_t* offs, int64_t n, int64_t total, int64_t* idx, hipStream_t s);
+
 // ------------------------------------------------------------ data movement
 // dst[idx] = src[idx] over `dims`, both operands addressed by element strides
 // (src strides may be 0 or negative; pointers already include the offsets).

@@ -29,7 +29,11 @@ def main():
     rng = np.random.default_rng(0)
     pts = rng.uniform(0, 1, (a.rows, a.features))
     df = tfs.analyze(tfs.from_columns({"features": pts}, num_partitions=4)).cache()
-    c0 = rng.standard_normal((a.k, a.features))
+    # the initial centers are k rows of the frame, drawn where the frame lives (about 20 k candidates,
+    # the first k of them; the same rows for every partitioning and number of ranks)
+    c0 = df.sample(min(1.0, 20.0 * a.k / a.rows), seed=0).limit(a.k).to_numpy("features")
+    if c0.shape[0] < a.k:
+        c0 = df.limit(a.k).to_numpy("features")
     for agg in (False, True):
         t0 = time.perf_counter()
         centers, dists = kmeans.kmeans(df, c0, num_iters=a.iters, tf_aggregate=agg)

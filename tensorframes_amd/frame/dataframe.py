@@ -30,6 +30,7 @@ from .block import (Block, ObjectColumn, RaggedColumn, StringColumn, build_colum
                     is_dense)
 from .column import Column, compile_expressions
 from .column_info import ColumnInformation, DataFrameInfo, explain_schema
+from .sampling import RandomExpression, refuse_random_expression
 from .window import WindowExpression, refuse_window_expression
 from .types import (ArrayType, BinaryType, BooleanType, DataType, DoubleType, FloatType, IntegerType,
                     LongType, NumericType, Row, StringType, StructField, StructType, scalar_type_of)
@@ -447,6 +448,8 @@ class DataFrame:
         field copied with all of its metadata. Computed expressions of one
         select run as ONE map_blocks over a generated graph."""
         names = [c for cs in cols for c in (cs if isinstance(cs, (list, tuple)) else [cs])]
+        if any(isinstance(n, RandomExpression) for n in names):
+            return self._select_randoms(names)
         if any(isinstance(n, WindowExpression) for n in names):
             return self._select_windows(names)
         if any(isinstance(n, Column) for n in names):
@@ -540,11 +543,53 @@ class DataFrame:
             seen.add(name)
         return apply_windows(self, outs, "select")
 
+    def _select_randoms(self, items: Sequence[Any]) -> "DataFrame":
+        """select with random expressions (`F.rand`, `F.randn`:
+        frame/sampling.py) next to names and plain column references."""
+        from .sampling import apply_randoms
+        outs: List[tuple] = []  # (output name, source column or the random expression)
+        for it in items:
+            if isinstance(it, RandomExpression):
+                outs.append((it.output_name, it))
+                continue
+            if isinstance(it, WindowExpression):
+                raise TypeError(f"select: the window expression '{it.output_name}' stands next to a random "
+                                f"expression; split the call: add one of them with withColumn first")
+            if isinstance(it, str):
+                it = Column._ref(it)
+            elif not isinstance(it, Column):
+                raise TypeError(f"select: a column name, a Column or a random expression is expected, got "
+                                f"{type(it).__name__}")
+            it._no_sort_order("select")
+            if not it.is_reference:
+                raise TypeError(f"select: the computed Column '{it.output_name}' stands next to a random expression; "
+                                f"split the call: add the random columns first (select or withColumn), then "
+                                f"compute with them")
+            if it._expr[1] not in self._schema:
+                raise ValueError(f"Column {it._expr[1]} not found in {self.columns}")
+            outs.append((it.output_name, it._expr[1]))
+        seen = set()
+        for name, _ in outs:
+            if name in seen:
+                raise ValueError(f"select: duplicate output column name '{name}'; give one of them an .alias()")
+            seen.add(name)
+        return apply_randoms(self, outs, "select")
+
     def withColumn(self, name: str, expr: Column) -> "DataFrame":  # noqa: N802
         """Appends column `name`; an existing column of that name is replaced
-        in place (keeps its position), as in Spark. `expr` is a Column or a
-        window expression (`F.row_number().over(w)`, `F.sum("x").over(w)`);
-        the latter gives the rows in the window's sort order."""
+        in place (keeps its position), as in Spark. `expr` is a Column, a
+        window expression (`F.row_number().over(w)`, `F.sum("x").over(w)`),
+        which gives the rows in the window's sort order, or a random
+        expression (`F.rand(seed)`, `F.randn(seed)`: one float64 draw per row,
+        rows and partitions as they are)."""
+        if isinstance(expr, RandomExpression):
+            from .sampling import apply_randoms
+            if not isinstance(name, str) or not name:
+                raise TypeError(f"withColumn: a non-empty column name is expected, got {name!r}")
+            outs = [(c, expr if c == name else c) for c in self.columns]
+            if name not in self._schema:
+                outs.append((name, expr))
+            return apply_randoms(self, outs, "withColumn")
         if isinstance(expr, WindowExpression):
             from .window import apply_windows
             if not isinstance(name, str) or not name:
@@ -718,6 +763,42 @@ class DataFrame:
         from .setops import _semi_frame
         return _semi_frame(self, other, "left_anti", "subtract")
 
+    def sample(self, withReplacement=None, fraction=None, seed=None) -> "DataFrame":  # noqa: N803
+        """A random subset of the rows, in Spark's call forms: `sample(0.1)`,
+        `sample(0.1, 3)`, `sample(False, 0.1, 3)`, `sample(fraction=0.1,
+        seed=3)`. Without replacement a row is kept when its uniform draw u is
+        below `fraction` (in [0, 1]); with replacement row i appears
+        Poisson(`fraction`) times, consecutively (`fraction` <= 16). Rows keep
+        their order and their partitions. A draw is a pure function of (seed,
+        global row index): the same rows for every number of ranks, every
+        partitioning of the same row sequence, on the host and on the device
+        (kernels/random.hip), and for every action on the frame, also with
+        `seed=None` (drawn once, when `sample` is called). docs/MIGRATION.md
+        has the generator in full."""
+        from .sampling import sample_frame
+        return sample_frame(self, withReplacement, fraction, seed)
+
+    def randomSplit(self, weights, seed=None) -> List["DataFrame"]:  # noqa: N802
+        """One frame per weight (positive, finite): the weights are normalised
+        to bounds 0 = b_0 <= ... <= b_k = 1 and split i keeps the rows with
+        b_i <= u < b_{i+1}, all under one seed, so every row lands in exactly
+        one split (see `sample` for u)."""
+        from .sampling import random_split
+        return random_split(self, weights, seed)
+
+    random_split = randomSplit
+
+    def sampleBy(self, col, fractions, seed=None) -> "DataFrame":  # noqa: N802
+        """A stratified sample: a row whose `col` value is key k is kept when
+        u < fractions[k] (a dict from key to a fraction in [0, 1]); keys not
+        in the dict are dropped, as in Spark. `col` is a numeric scalar
+        column under `orderBy`'s key rules; keys compare as there (NaN
+        matches NaN, -0.0 matches 0.0). At most 4096 strata."""
+        from .sampling import sample_by
+        return sample_by(self, col, fractions, seed)
+
+    sample_by = sampleBy
+
     def describe(self, *cols) -> "DataFrame":
         """count, mean, stddev, min and max of the named columns, or of every
         numeric scalar column (uint8, int8, int16, int32, int64, float,
@@ -820,6 +901,7 @@ class DataFrame:
 
     def groupBy(self, *cols) -> "GroupedData":  # noqa: N802
         names = [c for cs in cols for c in (cs if isinstance(cs, (list, tuple)) else [cs])]
+        refuse_random_expression("groupBy", names)
         for n in names:
             if n not in self._schema:
                 raise ValueError(f"groupBy: column {n} not found in {self.columns}")

@@ -362,6 +362,12 @@ class DataFrameStatFunctions:
     def cov(self, col1, col2):
         return _pair_statistic(self.df, "covar_samp", col1, col2, "pearson")
 
+    def sampleBy(self, col, fractions, seed=None):  # noqa: N802
+        """`DataFrame.sampleBy`: a stratified sample by the values of `col`."""
+        return self.df.sampleBy(col, fractions, seed)
+
+    sample_by = sampleBy
+
 
 def _pair_statistic(df, fn: str, col1, col2, method) -> float:
     """`df.stat.corr` / `df.stat.cov`: `DataFrame.agg` of one pair expression,

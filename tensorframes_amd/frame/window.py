@@ -209,7 +209,10 @@ class WindowExpression:
 
 
 def refuse_window_expression(what: str, items: Sequence[Any]) -> None:
-    """The TypeError of an operator that is given a window expression."""
+    """The TypeError of an operator that is given a window expression (or a
+    random expression, frame/sampling.py: the same rule)."""
+    from .sampling import refuse_random_expression
+    refuse_random_expression(what, items)
     for it in items:
         for x in (it if isinstance(it, (list, tuple)) else [it]):
             if isinstance(x, WindowExpression):

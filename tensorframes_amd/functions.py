@@ -18,7 +18,7 @@ from .frame.column import Column
 
 __all__ = ["AggregateExpression", "PairAggregateExpression", "count", "sum", "avg", "mean", "min", "max", "stddev",
            "stddev_samp", "stddev_pop", "variance", "var_samp", "var_pop", "corr", "covar_samp", "covar_pop",
-           "row_number", "rank", "dense_rank"]
+           "row_number", "rank", "dense_rank", "rand", "randn"]
 
 # the canonical statistic behind every accepted name (the dict form of agg uses the same table)
 FUNCTIONS = {
@@ -227,3 +227,20 @@ def rank() -> RankingFunction:
 def dense_rank() -> RankingFunction:
     """Distinct order-key tuples of the group up to the row's: 1, 1, 2, ... (int32)."""
     return RankingFunction("dense_rank")
+
+
+def rand(seed=None):
+    """One uniform float64 in [0, 1) per row, for `DataFrame.withColumn` /
+    `select`: a pure function of (seed, global row index), the same bits on
+    the host and on the device and for every number of ranks. `seed=None`
+    draws a seed when the column is added. No Column: add it first, then
+    compute with it."""
+    from .frame.sampling import RandomExpression
+    return RandomExpression("rand", seed)
+
+
+def randn(seed=None):
+    """One standard normal float64 per row (Box-Muller over the row's Philox
+    words; see `rand`)."""
+    from .frame.sampling import RandomExpression
+    return RandomExpression("randn", seed)
