@@ -1523,6 +1523,134 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "frames[o] (rows, range, whole), read from channel chans[o]. carry[c] / carry_rows: the fold of the first "
      "group's pieces in earlier partitions, applied on the left when has_carry; total[c] / total_rows: the whole-"
      "group values of the last group when it runs on into a later partition (has_total)");
+  // median / percentile / mode / countDistinct per group on device-resident partitions (kernels/group_order.hip)
+  m.def("group_order_chunk_rows", [] { return k::group_order_chunk_rows(); },
+        "rows per work item of group_order_summary");
+  // the words [W, n] of one sorted partition and 0 <= P <= W <= kMaxSortKeys
+  auto order_words = [window_table](const char* what, const at::Tensor& words, int64_t P) {
+    window_table(what, "the words", words);
+    const int64_t W = words.size(0);
+    if (W > k::kMaxSortKeys)
+      throw py::value_error(str_cat(what, ": at most ", k::kMaxSortKeys, " words per row, got ", W));
+    if (P < 0 || P > W) throw py::value_error(str_cat(what, ": 0 <= P <= ", W, " expected, got ", P));
+    if (words.size(1) >= (int64_t(1) << 31))
+      throw py::value_error(str_cat(what, ": ", words.size(1), " rows; a partition of 2^31 rows or more does not fit"));
+  };
+  m.def("group_order_summary", [order_words](const at::Tensor& words, int64_t P) {
+    order_words("group_order_summary", words, P);
+    const int64_t W = words.size(0), n = words.size(1);
+    const auto opts = words.options();
+    if (n == 0)  // nothing is launched
+      return py::make_tuple(at::zeros({1}, opts), at::empty({0}, opts), at::empty({0}, opts), at::empty({0}, opts));
+    c10::hip::HIPGuard guard(words.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(words.device().index()).stream();
+    int64_t ng = 1;
+    at::Tensor starts;
+    if (P > 0) {
+      const size_t ub = k::unique_workspace_bytes(n);
+      at::Tensor uws = pool_empty({static_cast<int64_t>((ub + 7) / 8)}, opts);
+      {
+        py::gil_scoped_release nogil;
+        ng = k::unique_plan(words.data_ptr<int64_t>(), static_cast<int>(P), n, nullptr, uws.data_ptr(),
+                            uws.numel() * 8, s);
+      }
+      starts = pool_empty({ng + 1}, opts);
+      k::unique_write(nullptr, n, ng, uws.data_ptr(), starts.data_ptr<int64_t>(), s);
+    } else {
+      starts = at::zeros({2}, opts);
+    }
+    starts.narrow(0, ng, 1).fill_(n);
+    at::Tensor distinct = pool_empty({ng}, opts), mode_pos = pool_empty({ng}, opts), mode_len = pool_empty({ng}, opts);
+    const size_t wsb = k::group_order_summary_workspace_bytes(n, ng);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 15) / 16) * 2}, opts);
+    {
+      py::gil_scoped_release nogil;
+      k::group_order_summary(W ? words.data_ptr<int64_t>() : nullptr, static_cast<int>(W), static_cast<int>(P), n,
+                             starts.data_ptr<int64_t>(), ng, distinct.data_ptr<int64_t>(),
+                             mode_pos.data_ptr<int64_t>(), mode_len.data_ptr<int64_t>(), ws.data_ptr(),
+                             static_cast<size_t>(ws.numel()) * 8, s);
+    }
+    return py::make_tuple(starts, distinct, mode_pos, mode_len);
+  }, py::arg("words"), py::arg("P"),
+     "the words [W, n] of one sorted partition (int64 device bit patterns; the first P define groups, all W peer "
+     "runs) -> (starts [ng + 1], distinct [ng], mode_pos [ng], mode_len [ng]), int64: the group heads in order with "
+     "starts[ng] = n, the peer heads per group, and the head row and the length of the group's first longest peer "
+     "run. A work item is at most group_order_chunk_rows() rows of one group; two stream synchronisations read the "
+     "group and the work item counts. The same bytes on every run. n == 0 launches nothing");
+  m.def("group_order_finish", [order_words](const at::Tensor& words, const at::Tensor& starts,
+                                            const at::Tensor& distinct, const at::Tensor& mode_pos,
+                                            const at::Tensor& mode_len, const std::vector<std::string>& fns,
+                                            const std::vector<std::vector<double>>& percentages,
+                                            at::ScalarType value_dtype) {
+    static const char* const fn_names[] = {"count_distinct", "mode", "percentile_approx", "percentile"};
+    order_words("group_order_finish", words, 0);
+    const int64_t W = words.size(0), n = words.size(1);
+    if (W < 1) throw py::value_error("group_order_finish: words [W, n] with W >= 1 expected; the last word is the value");
+    auto vec = [&](const at::Tensor& t, const char* which, int64_t len) {
+      if (!t.is_cuda() || t.device() != words.device())
+        throw py::value_error(str_cat("group_order_finish: ", which, " must be a device tensor on the words' device"));
+      if (t.scalar_type() != at::kLong)
+        throw py::type_error(str_cat("group_order_finish: ", which, " must be int64, got ", c10::toString(t.scalar_type())));
+      if (t.dim() != 1 || t.size(0) != len)
+        throw py::value_error(str_cat("group_order_finish: ", which, " must hold [", len, "] entries, got ", t.dim(),
+                                      "-D with ", t.numel()));
+      if (!t.is_contiguous()) throw py::value_error(str_cat("group_order_finish: ", which, " is not contiguous"));
+    };
+    if (starts.dim() != 1 || starts.size(0) < 1)
+      throw py::value_error("group_order_finish: starts [ng + 1] expected");
+    const int64_t ng = starts.size(0) - 1;
+    vec(starts, "starts", ng + 1);
+    vec(distinct, "distinct", ng);
+    vec(mode_pos, "mode_pos", ng);
+    vec(mode_len, "mode_len", ng);
+    if (ng > n) throw py::value_error(str_cat("group_order_finish: ", ng, " groups for ", n, " rows"));
+    if ((ng == 0) != (n == 0)) throw py::value_error(str_cat("group_order_finish: ", ng, " groups for ", n, " rows"));
+    if (fns.empty() || fns.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("group_order_finish: 1..", k::kMaxPackCols, " outputs per call, got ", fns.size()));
+    if (percentages.size() != fns.size())
+      throw py::value_error("group_order_finish: one list of percentages per output expected (empty for mode and "
+                            "count_distinct)");
+    require_stat_type(value_dtype, "group_order_finish: the value column is a ", " column");
+    k::GroupOrderSpec sp;
+    sp.n_out = static_cast<int>(fns.size());
+    sp.dtype = from_scalar_type(value_dtype);
+    c10::hip::HIPGuard guard(words.device().index());
+    std::vector<at::Tensor> outs;
+    for (size_t o = 0; o < fns.size(); ++o) {
+      const int fn = name_index(fn_names, fns[o]);
+      if (fn < 0) throw py::value_error(str_cat("group_order_finish: '", fns[o], "' is not an order aggregate"));
+      const auto gf = static_cast<k::GroupOrderFn>(fn);
+      const bool ranked = gf == k::GroupOrderFn::PERCENTILE_APPROX || gf == k::GroupOrderFn::PERCENTILE;
+      const auto& ps = percentages[o];
+      if (ranked ? (ps.empty() || ps.size() > static_cast<size_t>(k::kMaxPercentages)) : !ps.empty())
+        throw py::value_error(str_cat("group_order_finish: output ", o, " (", fns[o], ") takes ",
+                                      ranked ? "1..16 percentages" : "no percentages", ", got ", ps.size()));
+      for (double p : ps)
+        if (!(p >= 0.0 && p <= 1.0))
+          throw py::value_error(str_cat("group_order_finish: the percentage ", p, " is not in [0, 1]"));
+      sp.fn[o] = gf;
+      sp.nq[o] = ranked ? static_cast<int>(ps.size()) : 1;
+      for (int q = 0; q < k::kMaxPercentages; ++q) sp.pct[o][q] = q < static_cast<int>(ps.size()) ? ps[q] : 0.0;
+      const at::ScalarType ot = gf == k::GroupOrderFn::COUNT_DISTINCT ? at::kLong
+                                : gf == k::GroupOrderFn::PERCENTILE   ? at::kDouble
+                                                                      : value_dtype;
+      // (a list of percentages gives [ng, Q]; the frame layer squeezes a single one)
+      outs.push_back(ranked ? pool_empty({ng, static_cast<int64_t>(ps.size())}, words.options().dtype(ot))
+                            : pool_empty({ng}, words.options().dtype(ot)));
+      sp.out[o] = outs.back().data_ptr();
+    }
+    if (ng == 0) return outs;  // nothing is launched
+    k::group_order_finish(words.data_ptr<int64_t>() + (W - 1) * n, n, starts.data_ptr<int64_t>(),
+                          distinct.data_ptr<int64_t>(), mode_pos.data_ptr<int64_t>(), ng, sp,
+                          c10::hip::getCurrentHIPStream(words.device().index()).stream());
+    return outs;
+  }, py::arg("words"), py::arg("starts"), py::arg("distinct"), py::arg("mode_pos"), py::arg("mode_len"),
+     py::arg("fns"), py::arg("percentages"), py::arg("value_dtype"),
+     "the words [W, n] of one sorted partition (the last word is the value) and group_order_summary's result -> one "
+     "device tensor per output (up to 16, one launch): fns[o] of count_distinct (int64 [ng]), mode (value_dtype "
+     "[ng]), percentile_approx (value_dtype [ng, Q]: the element at rank max(ceil(p N) - 1, 0)) or percentile "
+     "(float64 [ng, Q]: Spark's linear interpolation, (hi - pos) v_lo + (pos - lo) v_hi without contraction), with "
+     "percentages[o] its Q in 1..16 percentages in [0, 1] (empty for the first two)");
   // DataFrame.sample / randomSplit / sampleBy, F.rand / F.randn (kernels/random.hip)
   m.def("random_tile_rows", [] { return k::random_tile_rows(); }, "rows per block of the random_* kernels");
   // options of a [n] output on `device` (-1: the current one), after the checks every draw shares

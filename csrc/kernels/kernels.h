@@ -465,6 +465,42 @@ struct WindowFinishSpec {
 // row (WHOLE; the total when the group runs on), decoded to the output column.
 void window_finish(const int64_t* fwd, const int64_t* rev, int64_t n, const WindowFinishSpec& spec, hipStream_t s);
 
+// ------------------------------------------------------------ holistic aggregates (group_order.hip)
+// median / percentile, percentile_approx, mode and countDistinct per group.
+// The n rows of one partition are sorted by (group keys, value columns) and
+// come as sort_encode's words [W][n]; the first P words define the groups, all
+// W the peer runs, the last word is the value. starts [ng + 1] lists the
+// group heads in order (unique_plan / unique_write over the first P words),
+// starts[ng] == n.
+int group_order_chunk_rows();  // rows per work item of group_order_summary
+size_t group_order_summary_workspace_bytes(int64_t n, int64_t ng);
+// per group: distinct = its peer heads, mode_len = the length of its longest
+// peer run and mode_pos that run's head row (among equal lengths the first).
+// window_scan's PEER_HEAD channel, then a work item is at most
+// group_order_chunk_rows() rows of one group, taken by one wave; a group's
+// items are folded by a second kernel. Integers only; group_items
+// synchronises the stream once. n < 2^31. n == 0 or ng == 0 launches nothing.
+void group_order_summary(const int64_t* words, int W, int P, int64_t n, const int64_t* starts, int64_t ng,
+                         int64_t* distinct, int64_t* mode_pos, int64_t* mode_len, void* workspace,
+                         size_t workspace_size, hipStream_t s);
+constexpr int kMaxPercentages = 16;
+enum class GroupOrderFn : int { COUNT_DISTINCT = 0, MODE, PERCENTILE_APPROX, PERCENTILE };
+struct GroupOrderSpec {
+  int n_out = 0;
+  GroupOrderFn fn[kMaxPackCols];
+  int nq[kMaxPackCols];                        // percentages of the output (1 for the others)
+  double pct[kMaxPackCols][kMaxPercentages];   // each in [0, 1]
+  void* out[kMaxPackCols];  // [ng] int64 (COUNT_DISTINCT), [ng] of dtype (MODE), [ng][nq] of dtype / of f64
+  DType dtype = DType::F32;  // of the value column
+};
+// one launch for all outputs. With N the rows of a group: PERCENTILE_APPROX is
+// the word at rank max(ceil(p N) - 1, 0); PERCENTILE is, with pos = p (N - 1),
+// lo = floor(pos), hi = ceil(pos), v_lo if lo == hi and otherwise
+// (hi - pos) v_lo + (pos - lo) v_hi in f64 without contraction (a NaN leaves as
+// the quiet NaN). value_words [n]: the last word of every row.
+void group_order_finish(const int64_t* value_words, int64_t n, const int64_t* starts, const int64_t* distinct,
+                        const int64_t* mode_pos, int64_t ng, const GroupOrderSpec& spec, hipStream_t s);
+
 // ------------------------------------------------------------ random draws (random.hip)
 // DataFrame.sample / randomSplit / sampleBy, F.rand / F.randn. Row i of a call
 // draws from Philox4x32-10 with the key (seed low, seed high) and the counter

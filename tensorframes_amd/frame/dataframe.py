@@ -1391,7 +1391,13 @@ class GroupedData:
         per call): NaN where Spark gives null, and for a group with a NaN or an
         infinity in either column. Device-resident partitions are reduced by
         the grouped-moments kernels (kernels/group_stats.hip); for a given
-        partitioning the result has the same bits for every number of ranks."""
+        partitioning the result has the same bits for every number of ranks.
+        `F.median`, `F.percentile`, `F.percentile_approx`, `F.mode`,
+        `F.countDistinct` and `F.approx_count_distinct` mix in as well
+        (frame/order_agg.py: one global sort per (keys, value columns),
+        kernels/group_order.hip); a call that holds only these returns its
+        rows in ascending key order, in this frame's number of partitions,
+        with the same bits for every partitioning."""
         from .group_agg import group_agg
         return group_agg(self, list(exprs))
 

@@ -452,6 +452,9 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
     from .._native import _C
     from ..ops import groupby as G
     from .dataframe import DataFrame, _Derived, tensor_field
+    from .order_agg import agg_with_order, has_order_aggregates
+    if has_order_aggregates(exprs):  # median, percentile, mode, countDistinct: frame/order_agg.py
+        return agg_with_order(grouped, exprs, what)
     df, keys = grouped.df, list(grouped.keys)
     specs = _specs(df, keys, exprs, what)
     if not keys:
