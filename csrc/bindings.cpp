@@ -963,6 +963,62 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "words [W, n] (sort_encode) in the stable order perm (sort_argsort; None: in order already) -> int64 [m]: "
      "perm[i] of every position i that starts a run of equal word tuples, in order (source row indices for "
      "take_rows); one stream synchronisation reads the count");
+  // groupBy().pivot().agg on device-resident partitions (kernels/pivot.hip)
+  m.def("pivot_block_threads", [] { return k::pivot_block_threads(); }, "threads per block of pivot_spread");
+  m.def("pivot_spread", [](const at::Tensor& offsets, const at::Tensor& pivot_words, const at::Tensor& value_words,
+                           const std::vector<at::Tensor>& vals, const std::vector<int64_t>& fills) {
+    auto words1d = [&](const at::Tensor& t, const char* name) {
+      if (!t.is_cuda()) throw py::value_error(str_cat("pivot_spread: ", name, " must be a device tensor"));
+      if (t.scalar_type() != at::kLong)
+        throw py::type_error(str_cat("pivot_spread: ", name, " must be int64, got ", c10::toString(t.scalar_type())));
+      if (t.device() != offsets.device())
+        throw py::value_error(str_cat("pivot_spread: ", name, " is not on the offsets' device"));
+      if (t.dim() != 1 || !t.is_contiguous())
+        throw py::value_error(str_cat("pivot_spread: ", name, " must be 1-D and contiguous"));
+    };
+    words1d(offsets, "offsets");
+    words1d(pivot_words, "pivot_words");
+    words1d(value_words, "value_words");
+    if (offsets.size(0) < 1)
+      throw py::value_error("pivot_spread: offsets [G + 1] expected, got an empty tensor");
+    const int64_t G = offsets.size(0) - 1, mm = pivot_words.size(0), V = value_words.size(0);
+    if (V > k::kMaxPivotValues)
+      throw py::value_error(str_cat("pivot_spread: at most ", k::kMaxPivotValues, " values per call, got ", V));
+    if (vals.empty() || vals.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("pivot_spread: 1..", k::kMaxPackCols, " outputs per call, got ", vals.size()));
+    if (fills.size() != vals.size())
+      throw py::value_error(str_cat("pivot_spread: ", fills.size(), " fills for ", vals.size(), " outputs"));
+    k::PivotSpreadCols pc;
+    pc.n = static_cast<int>(vals.size());
+    c10::hip::HIPGuard guard(offsets.device().index());
+    std::vector<at::Tensor> outs;
+    for (size_t a = 0; a < vals.size(); ++a) {
+      const at::Tensor& v = vals[a];
+      if (!v.is_cuda() || v.device() != offsets.device())
+        throw py::value_error(str_cat("pivot_spread: vals[", a, "] must be a device tensor on the offsets' device"));
+      if (v.element_size() != 4 && v.element_size() != 8)
+        throw py::type_error(str_cat("pivot_spread: vals[", a, "] has ", c10::toString(v.scalar_type()),
+                                     " elements; 4- or 8-byte elements expected"));
+      if (v.dim() != 1 || v.size(0) != mm || !v.is_contiguous())
+        throw py::value_error(str_cat("pivot_spread: vals[", a, "] must be contiguous [", mm,
+                                      "], one element per pivot word"));
+      outs.push_back(pool_empty({V, G}, v.options()));
+      if (v.element_size() == 8) pc.wide |= 1u << a;
+      pc.src[a] = v.data_ptr();
+      pc.dst[a] = outs.back().data_ptr();
+      pc.fill[a] = fills[a];
+    }
+    if (G > 0 && V > 0)
+      k::pivot_spread(offsets.data_ptr<int64_t>(), mm ? pivot_words.data_ptr<int64_t>() : nullptr,
+                      value_words.data_ptr<int64_t>(), G, mm, V, pc,
+                      c10::hip::getCurrentHIPStream(offsets.device().index()).stream());
+    return outs;
+  }, py::arg("offsets"), py::arg("pivot_words"), py::arg("value_words"), py::arg("vals"), py::arg("fills"),
+     "offsets int64 [G + 1] (CSR of the keys over the records), pivot_words int64 [m] (ascending as unsigned words "
+     "inside every key, each at most once), value_words int64 [V <= 1024], vals: 1..16 contiguous device columns [m] "
+     "of 4- or 8-byte elements, fills: one int64 bit pattern per column -> one tensor [V, G] per column: cell [j, g] "
+     "is vals[a] at the record of key g whose word is value_words[j], else the fill (its low 4 bytes for 4-byte "
+     "elements). Bit copies; every cell is written once, no atomics");
   // DataFrame.join on device-resident partitions (kernels/join.hip)
   m.def("join_tile_rows", [] { return k::join_tile_rows(); }, "output rows per block of join_expand");
   m.def("join_gather_words", [](const at::Tensor& words0, const at::Tensor& perm0) {

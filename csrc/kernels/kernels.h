@@ -263,6 +263,27 @@ int64_t unique_plan(const int64_t* words, int W, int64_t n, const int64_t* perm,
 void unique_write(const int64_t* perm, int64_t n, int64_t total, const void* workspace, int64_t* kept,
                   hipStream_t s);
 
+// ------------------------------------------------------------ pivot (pivot.hip)
+// groupBy(keys).pivot(p).agg(...): the long table, one record per (key, pivot
+// value) in ascending (keys..., pivot) order, spread to the wide one. offsets
+// [G + 1] is the CSR of the G keys over the m records, pivot_words [m] the
+// records' pivot sort words (ascending as unsigned words inside one key, each
+// at most once), value_words [V] the words of the output columns in their
+// order. Cell j * G + g of output a is src[a][r] of the record r of key g whose
+// word is value_words[j], fill[a] (its low 4 bytes for 4-byte elements) where
+// there is none: bit copies, every cell written exactly once.
+constexpr int kMaxPivotValues = 1024;
+struct PivotSpreadCols {
+  int n = 0;
+  uint32_t wide = 0;               // bit a: output a has 8-byte elements (else 4-byte)
+  const void* src[kMaxPackCols];   // [m], contiguous
+  void* dst[kMaxPackCols];         // [V][G]
+  int64_t fill[kMaxPackCols];
+};
+int pivot_block_threads();
+void pivot_spread(const int64_t* offsets, const int64_t* pivot_words, const int64_t* value_words, int64_t G, int64_t m,
+                  int64_t V, const PivotSpreadCols& pc, hipStream_t s);
+
 // ------------------------------------------------------------ join (join.hip)
 // DataFrame.join: an equi-join of two frames on key tuples. Keys are the words
 // of sort_encode (ascending), so equal words are Spark's key equality (NaN

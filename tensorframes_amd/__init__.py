@@ -27,6 +27,7 @@ from .frame.column import Column, asc, col, column, desc
 from .frame.dataframe import (DataFrame, GroupedData, create_dataframe, createDataFrame, from_columns,
                               generate, tensor_field)
 from .frame.window import Window, WindowExpression, WindowSpec
+from .frame.pivot import PivotedData
 from .frame.arrow_io import from_arrow, read_parquet, to_arrow, write_parquet
 from .frame.spark_io import from_spark, to_spark
 from .frame.checkpoint import read_checkpoint, write_checkpoint

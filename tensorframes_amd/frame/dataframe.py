@@ -861,10 +861,20 @@ class DataFrame:
         rows. An action, and collective."""
         return self.stat.cov(col1, col2)
 
+    def crosstab(self, col1, col2) -> "DataFrame":
+        """The contingency table of two numeric scalar columns
+        (`df.stat.crosstab`): `groupBy(col1).pivot(col2).count()` with the key
+        column renamed `<col1>_<col2>`. One row per value of `col1`, ascending,
+        one int64 column per distinct value of `col2` (ascending, NaN last),
+        0 for a pair that never occurs. Unlike Spark the first column keeps
+        `col1`'s numeric type. The distinct values of `col2` are looked up
+        when this is called (collective); the counts are lazy."""
+        return self.stat.crosstab(col1, col2)
+
     @property
     def stat(self):
         """Spark's `df.stat` accessor (`df.stat.approxQuantile(...)`,
-        `df.stat.corr(...)`, `df.stat.cov(...)`)."""
+        `df.stat.corr(...)`, `df.stat.cov(...)`, `df.stat.crosstab(...)`)."""
         from .stats import DataFrameStatFunctions
         return DataFrameStatFunctions(self)
 
@@ -1400,6 +1410,21 @@ class GroupedData:
         with the same bits for every partitioning."""
         from .group_agg import group_agg
         return group_agg(self, list(exprs))
+
+    def pivot(self, pivot_col, values=None):
+        """One output column per value of `pivot_col` (a name or a plain column
+        reference: an int32, int64, float or double scalar column that is no
+        grouping key): returns a `PivotedData` whose `agg`, `count`, `sum`,
+        `avg` / `mean`, `min` and `max` give one row per key and, per value,
+        one column per expression. `values` lists the values, in output order
+        (numbers that convert to the column's type without change; NaN is
+        allowed, -0.0 means 0.0, no value twice). Without it the distinct
+        values are looked up now (`select(pivot_col).distinct()`, collected:
+        eager and collective, as in Spark) and come ascending, NaN last. At
+        most 1024 values and 4096 output columns. `groupBy()` without keys
+        gives one row. See `PivotedData.agg` (frame/pivot.py)."""
+        from .pivot import pivot
+        return pivot(self, pivot_col, values)
 
     def sum(self, *cols) -> DataFrame:
         """`agg(F.sum(c), ...)` of the named columns, or of every numeric scalar column that is not a key."""

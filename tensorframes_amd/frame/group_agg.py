@@ -445,12 +445,95 @@ def _outputs(specs, scol, spair, vdt, merged, pmerged, on_device: bool) -> List[
     return outs
 
 
-# ------------------------------------------------------------------ keyed
-def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
-    """`GroupedData.agg`: see there."""
+# ------------------------------------------------------------------ both stages
+def _merged_records(blocks, keys: Sequence[str], n_route: int, vcols, pairs, single: bool, kdt, is_float,
+                    needed: Sequence[str], what: str):
+    """Stage 1 and stage 2 of a keyed aggregate over this rank's partitions:
+    (on_device, the distinct key columns [ng] in ascending lexicographic
+    order, merged records [ng, C, 6], merged pair records [ng, Q, 7]) of the
+    keys this rank answers for; a kind the call does not need is None. None
+    when no rank has rows, or none arrive here. Collective.
+
+    The first `n_route` keys decide the rank of a record (`GroupedData.agg`:
+    all of them; pivot: all but the pivot column, so a key's pivot values meet
+    on one rank; none: everything goes to rank 0); the other keys ride as
+    columns."""
     from .. import engine
     from .._native import _C
     from ..ops import groupby as G
+    C = max(len(vcols), 1) if single else 0
+    Q = len(pairs)
+    W1, W = C * _FIELDS, C * _FIELDS + Q * _PFIELDS  # a group's row: its records, then its pair records
+    parts = [(pid, b) for pid, b in sorted(blocks.items()) if b.nrows]
+    # decided together, so every rank takes the same (collective) path:
+    # the device path when no rank holds a needed column on the host
+    flags = torch.tensor([int(any(not _block_on_device(b, needed) for _, b in parts)), int(bool(parts))],
+                         dtype=torch.int64)
+    dist.all_reduce_host_(flags, "Max")
+    if not int(flags[1]):
+        return None
+    on_device = engine.gpu_available() and not int(flags[0])
+    dev = engine.compute_device() if on_device else torch.device("cpu")
+    got = []
+    for pid, b in parts:
+        u, r, pr = _partition_records(b, keys, vcols, on_device, what, pairs, single)
+        ng = int((r if r is not None else pr).shape[0])
+        row = [t.reshape(ng, -1) for t in (r, pr) if t is not None]
+        got.append((pid, u, row[0] if len(row) == 1 else torch.cat(row, dim=1)))
+    if got:
+        K = [engine.cat_rows([u[j] for _, u, _ in got]) for j in range(len(keys))]
+        R = engine.cat_rows([r for _, _, r in got])
+        pids = engine.cat_rows([engine.device_full(r.shape[0], pid, torch.int64, dev) for pid, _, r in got])
+    else:
+        K = [engine.device_empty(0, t, dev) for t in kdt]
+        R = engine.device_empty((0, W), torch.int64, dev)
+        pids = engine.device_empty(0, torch.int64, dev)
+
+    def split(rows):
+        """rows [m, W] -> (records [m, C, 6], pair records [m, Q, 7]); a kind without columns is None"""
+        m = int(rows.shape[0])
+        return (rows[:, :W1].contiguous().reshape(m, C, _FIELDS) if C else None,
+                rows[:, W1:].contiguous().reshape(m, Q, _PFIELDS) if Q else None)
+    if not dist.is_distributed() and len(got) == 1:
+        merged, pmerged = split(R)  # one partition: its records are the result
+        return on_device, K, merged, pmerged
+    if dist.is_distributed():
+        recv = G.route(K[:n_route], K[n_route:] + [pids, R])
+        K, pids, R = recv[:len(keys)], recv[len(keys)], recv[len(keys) + 1]
+    m = int(K[0].shape[0])
+    if m == 0:
+        return None
+    # (keys..., partition id) in lexicographic order: the records of one
+    # key are consecutive and in partition order
+    ids, uniq, m2 = G.group_ids([k.contiguous() for k in K] + [pids])
+    if m2 != m:
+        raise RuntimeError(f"{what}: {m} records but {m2} distinct (key, partition) pairs")
+    ordered = engine.device_empty((m, W), torch.int64, dev)
+    if on_device:
+        _C.scatter_rows(ordered, ids, R.contiguous())
+    else:
+        ordered[ids] = R
+    ids2, ukeys, ng = G.group_ids([u.contiguous() for u in uniq[:-1]])
+    recs, precs = split(ordered)
+    merged = pmerged = None
+    if on_device:
+        _, offsets = _C.segment_csr(ids2, ng)
+        if C:
+            merged = _C.merge_group_records(recs, offsets, is_float)
+        if Q:
+            pmerged = _C.merge_pair_records(precs, offsets)
+    else:
+        offsets = np.concatenate([[0], np.cumsum(np.bincount(ids2.numpy(), minlength=ng))]).astype(np.int64)
+        if C:
+            merged = torch.from_numpy(_merge_records(recs.numpy(), offsets, is_float))
+        if Q:
+            pmerged = torch.from_numpy(_merge_pair_records(precs.numpy(), offsets))
+    return on_device, ukeys, merged, pmerged
+
+
+# ------------------------------------------------------------------ keyed
+def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
+    """`GroupedData.agg`: see there."""
     from .dataframe import DataFrame, _Derived, tensor_field
     from .order_agg import agg_with_order, has_order_aggregates
     if has_order_aggregates(exprs):  # median, percentile, mode, countDistinct: frame/order_agg.py
@@ -462,9 +545,6 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
     _check_keys(df, keys, what)
     vcols, pairs = _columns_of(specs, what)
     single = any(s.pair is None for s in specs)
-    C = max(len(vcols), 1) if single else 0
-    Q = len(pairs)
-    W1, W = C * _FIELDS, C * _FIELDS + Q * _PFIELDS  # a group's row: its records, then its pair records
     vdt = ([D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]) if single else []
     is_float = [t.is_floating_point for t in vdt]
     kdt = [D.torch_dtype(_tf_dtype(df, k)) for k in keys]
@@ -482,71 +562,10 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
         return {p: Block(0, dict(cols)) for p in dist.local_partitions(world)}
 
     def compute(blocks):
-        parts = [(pid, b) for pid, b in sorted(blocks.items()) if b.nrows]
-        # decided together, so every rank takes the same (collective) path:
-        # the device path when no rank holds a needed column on the host
-        flags = torch.tensor([int(any(not _block_on_device(b, needed) for _, b in parts)), int(bool(parts))],
-                             dtype=torch.int64)
-        dist.all_reduce_host_(flags, "Max")
-        if not int(flags[1]):
+        got = _merged_records(blocks, keys, len(keys), vcols, pairs, single, kdt, is_float, needed, what)
+        if got is None:
             return empty()
-        on_device = engine.gpu_available() and not int(flags[0])
-        dev = engine.compute_device() if on_device else torch.device("cpu")
-        got = []
-        for pid, b in parts:
-            u, r, pr = _partition_records(b, keys, vcols, on_device, what, pairs, single)
-            ng = int((r if r is not None else pr).shape[0])
-            row = [t.reshape(ng, -1) for t in (r, pr) if t is not None]
-            got.append((pid, u, row[0] if len(row) == 1 else torch.cat(row, dim=1)))
-        if got:
-            K = [engine.cat_rows([u[j] for _, u, _ in got]) for j in range(len(keys))]
-            R = engine.cat_rows([r for _, _, r in got])
-            pids = engine.cat_rows([engine.device_full(r.shape[0], pid, torch.int64, dev) for pid, _, r in got])
-        else:
-            K = [engine.device_empty(0, t, dev) for t in kdt]
-            R = engine.device_empty((0, W), torch.int64, dev)
-            pids = engine.device_empty(0, torch.int64, dev)
-
-        def split(rows):
-            """rows [m, W] -> (records [m, C, 6], pair records [m, Q, 7]); a kind without columns is None"""
-            m = int(rows.shape[0])
-            return (rows[:, :W1].contiguous().reshape(m, C, _FIELDS) if C else None,
-                    rows[:, W1:].contiguous().reshape(m, Q, _PFIELDS) if Q else None)
-        if not dist.is_distributed() and len(got) == 1:
-            ukeys = K
-            merged, pmerged = split(R)  # one partition: its records are the result
-        else:
-            if dist.is_distributed():
-                recv = G.route(K, [pids, R])
-                K, pids, R = recv[:len(keys)], recv[len(keys)], recv[len(keys) + 1]
-            m = int(K[0].shape[0])
-            if m == 0:
-                return empty()
-            # (keys..., partition id) in lexicographic order: the records of one
-            # key are consecutive and in partition order
-            ids, uniq, m2 = G.group_ids([k.contiguous() for k in K] + [pids])
-            if m2 != m:
-                raise RuntimeError(f"{what}: {m} records but {m2} distinct (key, partition) pairs")
-            ordered = engine.device_empty((m, W), torch.int64, dev)
-            if on_device:
-                _C.scatter_rows(ordered, ids, R.contiguous())
-            else:
-                ordered[ids] = R
-            ids2, ukeys, ng = G.group_ids([u.contiguous() for u in uniq[:-1]])
-            recs, precs = split(ordered)
-            merged = pmerged = None
-            if on_device:
-                _, offsets = _C.segment_csr(ids2, ng)
-                if C:
-                    merged = _C.merge_group_records(recs, offsets, is_float)
-                if Q:
-                    pmerged = _C.merge_pair_records(precs, offsets)
-            else:
-                offsets = np.concatenate([[0], np.cumsum(np.bincount(ids2.numpy(), minlength=ng))]).astype(np.int64)
-                if C:
-                    merged = torch.from_numpy(_merge_records(recs.numpy(), offsets, is_float))
-                if Q:
-                    pmerged = torch.from_numpy(_merge_pair_records(precs.numpy(), offsets))
+        on_device, ukeys, merged, pmerged = got
         ng = int((merged if merged is not None else pmerged).shape[0])
         outs = _outputs(specs, scol, spair, vdt, merged, pmerged, on_device)
         keep = on_device and keep_on_device

@@ -362,6 +362,11 @@ class DataFrameStatFunctions:
     def cov(self, col1, col2):
         return _pair_statistic(self.df, "covar_samp", col1, col2, "pearson")
 
+    def crosstab(self, col1, col2):
+        """`DataFrame.crosstab`: the contingency table of two columns."""
+        from .pivot import crosstab
+        return crosstab(self.df, col1, col2)
+
     def sampleBy(self, col, fractions, seed=None):  # noqa: N802
         """`DataFrame.sampleBy`: a stratified sample by the values of `col`."""
         return self.df.sampleBy(col, fractions, seed)

@@ -66,7 +66,8 @@ def group_ids(keys: List[torch.Tensor]) -> Tuple[torch.Tensor, List[torch.Tensor
 
 
 def route(keys: List[torch.Tensor], cols: List[torch.Tensor], strings: Optional[Sequence] = None):
-    """Keyed all-to-all: rows go to rank hash(keys) % world; returns the
+    """Keyed all-to-all: rows go to rank hash(keys) % world (no keys: every
+    row goes to rank 0, the other columns still travel); returns the
     received columns (keys first, then `cols`), concatenated in source-rank
     order. With `strings` (string columns row-aligned with the keys: the
     hashed string keys' strings, host or device) returns (columns, their
@@ -79,12 +80,18 @@ def route(keys: List[torch.Tensor], cols: List[torch.Tensor], strings: Optional[
     dev = allc[0].device
     n = allc[0].shape[0]
     if dev.type == "cuda":
-        dest = _C.key_dest([k.contiguous() for k in keys], w) if n else engine_empty(0, torch.int64, dev)
+        if not keys:  # nothing to hash: every row goes to rank 0
+            dest = torch.zeros(n, dtype=torch.int64, device=dev)
+        else:
+            dest = _C.key_dest([k.contiguous() for k in keys], w) if n else engine_empty(0, torch.int64, dev)
         perm, counts = _C.partition_rows(dest, w)
         send_rows = [int(c) for c in counts.cpu().tolist()]
     else:
         from ..core import _key_hash
-        dest = (_key_hash([k.numpy() for k in keys]) % np.uint64(w)).astype(np.int64) if n else np.zeros(0, np.int64)
+        if not keys:
+            dest = np.zeros(n, np.int64)
+        else:
+            dest = (_key_hash([k.numpy() for k in keys]) % np.uint64(w)).astype(np.int64) if n else np.zeros(0, np.int64)
         perm = torch.from_numpy(np.argsort(dest, kind="stable"))
         send_rows = np.bincount(dest, minlength=w).tolist()
     recv_rows = dist.all_to_all_counts(send_rows)
