@@ -1435,6 +1435,162 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "stats[o] (corr, covar_samp, covar_pop) of pair pairs[o]. covar_pop = C / n (NaN without rows), covar_samp = "
      "C / (n - 1) (NaN below two rows), corr = C / sqrt(M2_x * M2_y) (NaN without rows or where an M2 is 0, not "
      "clamped); NaN where the record counts a row with a NaN or an infinity");
+  // skewness / kurtosis on device-resident columns (kernels/stats.hip, kernels/group_stats.hip)
+  // int64 device high records [*, C, 6], contiguous
+  auto high_records = [](const char* what, const at::Tensor& t) {
+    if (!t.is_cuda()) throw py::value_error(str_cat(what, ": the records must be a device tensor"));
+    if (t.scalar_type() != at::kLong) throw py::type_error(str_cat(what, ": the records must be int64 bit patterns"));
+    if (t.dim() != 3 || t.size(2) != k::kHighRecordFields || t.size(1) < 1 || t.size(1) > k::kMaxPackCols)
+      throw py::value_error(str_cat(what, ": records [*, 1..", k::kMaxPackCols, ", ", k::kHighRecordFields,
+                                    "] expected"));
+    if (!t.is_contiguous()) throw py::value_error(str_cat(what, ": the records are not contiguous"));
+  };
+  m.def("column_high_moments", [](const std::vector<at::Tensor>& cols) {
+    const k::StatCols sc = stat_cols_from("column_high_moments", cols);
+    const int64_t n = cols[0].size(0), C = sc.n;
+    const auto dev = cols[0].device();
+    if (n == 0) return at::zeros({C, k::kHighRecordFields}, at::kLong).to(dev);  // nothing is launched
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    at::Tensor rec = pool_empty({C, k::kHighRecordFields}, cols[0].options().dtype(at::kLong));
+    const size_t wsb = k::column_high_moments_workspace_bytes(sc.n, n);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, cols[0].options().dtype(at::kLong));
+    k::column_high_moments(sc, n, rec.data_ptr<int64_t>(), ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    return rec;
+  }, py::arg("cols"),
+     "up to 16 dense scalar device columns [n] (mixed dtypes, contiguous) -> int64 records [C, 6] (bit patterns): n, "
+     "mean, M2, M3, M4 (Mk = sum (x - mean)^k) as f64 and the count of rows that are NaN or an infinity; the same "
+     "bits on every run. n == 0 launches nothing and gives empty records (all zeros)");
+  // the CSR of a grouped call: perm [n] and offsets [nseg + 1] on the columns' device; returns nseg
+  auto group_csr = [group_index](const char* what, const at::Tensor& perm, const at::Tensor& offsets,
+                                 const at::Device& dev, int64_t n) {
+    group_index(what, "perm", perm, dev);
+    group_index(what, "offsets", offsets, dev);
+    if (perm.size(0) != n)
+      throw py::value_error(str_cat(what, ": perm has ", perm.size(0), " entries, the columns ", n, " rows"));
+    if (offsets.size(0) < 1) throw py::value_error(str_cat(what, ": offsets [nseg + 1] expected, got none"));
+    return offsets.size(0) - 1;
+  };
+  m.def("group_high_moments", [group_csr](const std::vector<at::Tensor>& cols, const at::Tensor& perm,
+                                          const at::Tensor& offsets) {
+    const k::StatCols sc = stat_cols_from("group_high_moments", cols);
+    const auto dev = cols[0].device();
+    const int64_t n = cols[0].size(0), C = sc.n;
+    const int64_t nseg = group_csr("group_high_moments", perm, offsets, dev, n);
+    if (n == 0 || nseg == 0) return at::zeros({nseg, C, k::kHighRecordFields}, at::kLong).to(dev);
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    at::Tensor rec = pool_empty({nseg, C, k::kHighRecordFields}, cols[0].options().dtype(at::kLong));
+    const size_t wsb = k::group_high_moments_workspace_bytes(sc.n, n, nseg);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wsb + 7) / 8)}, cols[0].options().dtype(at::kLong));
+    {
+      py::gil_scoped_release nogil;
+      k::group_high_moments(sc, n, perm.data_ptr<int64_t>(), n, offsets.data_ptr<int64_t>(), nseg,
+                            rec.data_ptr<int64_t>(), ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    }
+    return rec;
+  }, py::arg("cols"), py::arg("perm"), py::arg("offsets"),
+     "up to 16 dense scalar device columns [n] and segment_csr's (perm [n], offsets [nseg + 1]) -> int64 high records "
+     "[nseg, C, 6] (column_high_moments' fields). group_moments' work items; a record depends on its segment's rows "
+     "in row order alone. n == 0 launches nothing and gives empty records");
+  m.def("group_all_moments", [pair_cols_from, group_csr](const std::vector<at::Tensor>& cols,
+                                                         const std::vector<at::Tensor>& xs,
+                                                         const std::vector<at::Tensor>& ys,
+                                                         const std::vector<at::Tensor>& hcols, const at::Tensor& perm,
+                                                         const at::Tensor& offsets) {
+    const k::StatCols sh = stat_cols_from("group_all_moments", hcols);
+    const auto dev = hcols[0].device();
+    const int64_t n = hcols[0].size(0), H = sh.n;
+    k::StatCols sc, sx, sy;
+    if (!cols.empty()) sc = stat_cols_from("group_all_moments", cols);
+    if (!xs.empty() || !ys.empty()) pair_cols_from("group_all_moments", xs, ys, &sx, &sy);
+    for (const auto* first : {cols.empty() ? nullptr : &cols[0], xs.empty() ? nullptr : &xs[0]})
+      if (first && (first->device() != dev || first->size(0) != n))
+        throw py::value_error("group_all_moments: the columns are not all on one device and of one length");
+    const int64_t nseg = group_csr("group_all_moments", perm, offsets, dev, n);
+    const int64_t C = sc.n, Q = sx.n;
+    py::object none = py::none();
+    if (n == 0 || nseg == 0) {
+      at::Tensor rec = at::zeros({nseg, std::max<int64_t>(C, 1), k::kGroupRecordFields}, at::kLong);
+      if (nseg) rec.select(2, 4).fill_(-1);  // (all ones)
+      return py::make_tuple(C ? py::cast(rec.to(dev)) : none,
+                            Q ? py::cast(at::zeros({nseg, Q, k::kPairRecordFields}, at::kLong).to(dev)) : none,
+                            at::zeros({nseg, H, k::kHighRecordFields}, at::kLong).to(dev));
+    }
+    c10::hip::HIPGuard guard(dev.index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(dev.index()).stream();
+    const auto opts = hcols[0].options().dtype(at::kLong);
+    at::Tensor rec, prec, hrec = pool_empty({nseg, H, k::kHighRecordFields}, opts);
+    if (C) rec = pool_empty({nseg, C, k::kGroupRecordFields}, opts);
+    if (Q) prec = pool_empty({nseg, Q, k::kPairRecordFields}, opts);
+    const size_t ib = k::group_items_workspace_bytes(nseg);
+    const size_t wb = std::max({k::group_moments_workspace_bytes(sc.n, n, nseg),
+                                k::group_pair_moments_workspace_bytes(sx.n, n, nseg),
+                                k::group_high_moments_workspace_bytes(sh.n, n, nseg)});
+    at::Tensor wi = pool_empty({static_cast<int64_t>((ib + 7) / 8)}, opts);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((wb + 7) / 8)}, opts);
+    {
+      py::gil_scoped_release nogil;
+      // the work items are built once; the passes run in stream order and share the workspace of partial records
+      const int64_t* pp = perm.data_ptr<int64_t>();
+      const int64_t* po = offsets.data_ptr<int64_t>();
+      const size_t wsz = static_cast<size_t>(ws.numel()) * 8;
+      const k::GroupItems items = k::group_items(po, nseg, n, wi.data_ptr(), static_cast<size_t>(wi.numel()) * 8, s);
+      if (C) k::group_moments(sc, n, pp, n, po, nseg, rec.data_ptr<int64_t>(), ws.data_ptr(), wsz, s, &items);
+      if (Q) k::group_pair_moments(sx, sy, n, pp, n, po, nseg, prec.data_ptr<int64_t>(), ws.data_ptr(), wsz, s, &items);
+      k::group_high_moments(sh, n, pp, n, po, nseg, hrec.data_ptr<int64_t>(), ws.data_ptr(), wsz, s, &items);
+    }
+    return py::make_tuple(C ? py::cast(rec) : none, Q ? py::cast(prec) : none, hrec);
+  }, py::arg("cols"), py::arg("xs"), py::arg("ys"), py::arg("hcols"), py::arg("perm"), py::arg("offsets"),
+     "group_high_moments(hcols, perm, offsets) with group_moments(cols, ...) and / or group_pair_moments(xs, ys, ...) "
+     "of one CSR (cols or the pairs may be empty) -> (records [nseg, C, 6] or None, pair records [nseg, Q, 7] or "
+     "None, high records [nseg, H, 6]), the same bits as the separate calls; the work items (chunk counts and their "
+     "scan, one stream synchronisation) are built once for all");
+  m.def("merge_high_records", [high_records, group_index](const at::Tensor& recs, const at::Tensor& offsets) {
+    high_records("merge_high_records", recs);
+    group_index("merge_high_records", "offsets", offsets, recs.device());
+    const int64_t mm = recs.size(0), C = recs.size(1);
+    if (offsets.size(0) < 1) throw py::value_error("merge_high_records: offsets [ng + 1] expected, got none");
+    const int64_t ng = offsets.size(0) - 1;
+    c10::hip::HIPGuard guard(recs.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(recs.device().index()).stream();
+    at::Tensor out = pool_empty({ng, C, k::kHighRecordFields}, recs.options());
+    k::merge_high_records(mm ? recs.data_ptr<int64_t>() : nullptr, mm, static_cast<int>(C),
+                          offsets.data_ptr<int64_t>(), ng, out.data_ptr<int64_t>(), s);
+    return out;
+  }, py::arg("records"), py::arg("offsets"),
+     "high records [m, C, 6] ordered by (key, partition) and CSR offsets [ng + 1] over them -> [ng, C, 6]: each "
+     "group's records merged in order with Pébay's formulas (the non-finite counts add)");
+  m.def("high_results", [high_records](const at::Tensor& recs, const std::vector<int64_t>& cols,
+                                       const std::vector<std::string>& stats) {
+    static const char* const names[] = {"skewness", "kurtosis"};
+    high_records("high_results", recs);
+    const int64_t ng = recs.size(0), C = recs.size(1);
+    if (cols.empty() || cols.size() > static_cast<size_t>(k::kMaxPackCols))
+      throw py::value_error(str_cat("high_results: 1..", k::kMaxPackCols, " outputs per call, got ", cols.size()));
+    if (stats.size() != cols.size()) throw py::value_error("high_results: one statistic per output expected");
+    k::HighResultSpec spec;
+    spec.n = static_cast<int>(cols.size());
+    c10::hip::HIPGuard guard(recs.device().index());
+    std::vector<at::Tensor> outs;
+    for (size_t o = 0; o < cols.size(); ++o) {
+      if (cols[o] < 0 || cols[o] >= C)
+        throw py::value_error(str_cat("high_results: output ", o, " names column ", cols[o], " of ", C));
+      const int st = name_index(names, stats[o]);
+      if (st < 0) throw py::value_error(str_cat("high_results: '", stats[o], "' is not a high-moment statistic"));
+      outs.push_back(pool_empty({ng}, recs.options().dtype(at::kDouble)));
+      spec.col[o] = static_cast<int>(cols[o]);
+      spec.stat[o] = static_cast<k::HighStat>(st);
+      spec.out[o] = outs.back().data_ptr<double>();
+    }
+    k::high_results(ng ? recs.data_ptr<int64_t>() : nullptr, ng, static_cast<int>(C), spec,
+                    c10::hip::getCurrentHIPStream(recs.device().index()).stream());
+    return outs;
+  }, py::arg("records"), py::arg("cols"), py::arg("stats"),
+     "merged high records [ng, C, 6] -> one float64 device column [ng] per output (up to 16, one launch): output o is "
+     "stats[o] (skewness, kurtosis) of record column cols[o]. skewness = sqrt(n) M3 / M2^1.5, kurtosis = n M4 / M2^2 "
+     "- 3 (the excess, from population moments); NaN without rows, where M2 is 0 (one row included) and where the "
+     "record counts a row with a NaN or an infinity");
   // Window / .over() on device-resident partitions (kernels/window_scan.hip)
   m.def("window_tile_rows", [] { return k::window_tile_rows(); }, "rows per tile of window_scan");
   // int64 device bit patterns [rows, n], contiguous

@@ -39,6 +39,12 @@
 //            them for both), both columns gathered through perm, Welford per
 //            lane, pair records merged in lane, chunk and partition order.
 //
+//   high     group_high_moments, merge_high_records and high_results are those
+//            three steps again for the high-moments record of moments.h
+//            (skewness / kurtosis): one column gathered through perm, Welford's
+//            one-row update of M2, M3 and M4 per lane, Pébay's merge in lane,
+//            chunk and partition order.
+//
 // No float atomics, no inter-block communication, every loop bounded by the
 // row count.
 #include <algorithm>
@@ -462,6 +468,128 @@ __global__ __launch_bounds__(kT) void pair_results_kernel(const int64_t* __restr
   spec.out[o][g] = r.bad > 0 ? nan : v;
 }
 
+// ------------------------------------------------------------------ high moments
+namespace {
+
+// one lane's high record of rows perm[lo + lane], perm[lo + lane + 64], ...
+// below hi of one column (lane_rows' walk: the kLaneRows indices, then the
+// kLaneRows values, are loaded before the first update)
+template <typename T>
+__device__ __forceinline__ HighRec lane_high_rows(const void* __restrict__ src, const int64_t* __restrict__ perm,
+                                                  int64_t lo, int64_t hi, int64_t n, int lane) {
+  HighRec r = high_empty();
+  for (int64_t row = lo + lane; row < hi; row += kLaneRows * kWave) {
+    int64_t idx[kLaneRows];
+    double x[kLaneRows];
+#pragma unroll
+    for (int j = 0; j < kLaneRows; ++j) {
+      const int64_t rr = row + j * kWave;
+      idx[j] = rr < hi ? perm[rr] : -1;
+    }
+    gather_rows<T>(src, idx, n, x);
+#pragma unroll
+    for (int j = 0; j < kLaneRows; ++j) {
+      if (idx[j] >= 0 && idx[j] < n) high_add_row(r, x[j]);
+    }
+  }
+  return r;
+}
+
+}  // namespace
+
+// group_moments_kernel for high records: wave w of block (b, c) takes item
+// b * kWaves + w of column c -> part[item][c]
+__global__ __launch_bounds__(kT) void group_high_moments_kernel(StatCols cols, int64_t n,
+                                                                const int64_t* __restrict__ perm, int64_t nperm,
+                                                                const int64_t* __restrict__ offsets,
+                                                                const int64_t* __restrict__ coffs, int64_t nseg,
+                                                                int64_t items, int64_t* __restrict__ part) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int c = blockIdx.y;
+  const int64_t item = (int64_t)blockIdx.x * kWaves +
+                       __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x / kWave));
+  if (item >= items) return;  // (the whole wave)
+  const int64_t g = last_not_above(coffs, 0, 0, nseg - 1, item);
+  const int64_t ch = item - coffs[g];
+  const int64_t a = clamp64(offsets[g], 0, nperm), b = clamp64(offsets[g + 1], a, nperm);
+  const int64_t lo = clamp64(a + ch * kGroupChunk, a, b);
+  const int64_t hi = lo + kGroupChunk < b ? lo + kGroupChunk : b;
+  const void* src = cols.ptr[c];
+  // (the dtype is uniform: one scalar branch per block)
+  HighRec r = dispatch_column(cols.dtype[c],
+                              [&](auto tag) { return lane_high_rows<decltype(tag)>(src, perm, lo, hi, n, lane); });
+  r = wave_merge_high(r, hi - lo);  // a short chunk stops early
+  if (lane == 0) store_high(part + (item * gridDim.y + c) * kHighRecordFields, r);
+}
+
+// group_fold_kernel for high records: thread (g, c) folds part[coffs[g] ..
+// coffs[g + 1])[c] in chunk order -> out[g][c]; a segment of more than
+// kFoldSerial chunks is folded by the thread's wave, lane l the l-th run of
+// consecutive chunks, the lanes in lane order: still chunk order, and a
+// function of the segment's chunk count alone
+__global__ __launch_bounds__(kT) void group_high_fold_kernel(int C, const int64_t* __restrict__ part,
+                                                             const int64_t* __restrict__ coffs, int64_t nseg,
+                                                             int64_t items, int64_t* __restrict__ out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t t = (int64_t)blockIdx.x * kT + threadIdx.x;
+  const bool valid = t < nseg * C;
+  const int64_t g = valid ? t / C : 0;
+  const int c = valid ? static_cast<int>(t - g * C) : 0;
+  const int64_t a = clamp64(coffs[g], 0, items - 1), b = clamp64(coffs[g + 1], a + 1, items);
+  const bool wide = valid && b - a > kFoldSerial;
+  if (valid && !wide) {
+    HighRec r = load_high(part + (a * C + c) * kHighRecordFields);
+    for (int64_t i = a + 1; i < b; ++i) r = merge_high(r, load_high(part + (i * C + c) * kHighRecordFields));
+    store_high(out + t * kHighRecordFields, r);
+  }
+  unsigned long long todo = __ballot(wide);  // (the same in every lane: at most 64 rounds)
+  while (todo) {
+    const int src = __ffsll(todo) - 1;
+    todo &= todo - 1;
+    const int64_t sa = __shfl(static_cast<long long>(a), src, kWave);
+    const int64_t sb = __shfl(static_cast<long long>(b), src, kWave);
+    const int64_t st = __shfl(static_cast<long long>(t), src, kWave);
+    const int sc = __shfl(c, src, kWave);
+    const int64_t per = (sb - sa + kWave - 1) / kWave;
+    const int64_t i0 = sa + lane * per < sb ? sa + lane * per : sb, i1 = i0 + per < sb ? i0 + per : sb;
+    HighRec r = high_empty();
+    if (i0 < i1) r = load_high(part + (i0 * C + sc) * kHighRecordFields);
+    for (int64_t i = i0 + 1; i < i1; ++i) r = merge_high(r, load_high(part + (i * C + sc) * kHighRecordFields));
+    r = wave_merge_high(r);
+    if (lane == 0) store_high(out + st * kHighRecordFields, r);
+  }
+}
+
+// thread (g, c): recs[offsets[g] .. offsets[g + 1])[c] merged in order -> out[g][c]
+__global__ __launch_bounds__(kT) void merge_high_records_kernel(const int64_t* __restrict__ recs, int64_t m, int C,
+                                                                const int64_t* __restrict__ offsets, int64_t ng,
+                                                                int64_t* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (t >= ng * C) return;
+  const int64_t g = t / C;
+  const int c = static_cast<int>(t - g * C);
+  const int64_t a = clamp64(offsets[g], 0, m), b = clamp64(offsets[g + 1], a, m);
+  HighRec r = high_empty();
+  if (a < b) r = load_high(recs + (a * C + c) * kHighRecordFields);
+  for (int64_t i = a + 1; i < b; ++i) r = merge_high(r, load_high(recs + (i * C + c) * kHighRecordFields));
+  store_high(out + t * kHighRecordFields, r);
+}
+
+// thread g of block (.., o): output o of group g. NaN without rows, where M2
+// is 0 (a constant group, one row included) and where the record counts a row
+// with a NaN or an infinity, whichever row it was
+__global__ __launch_bounds__(kT) void high_results_kernel(const int64_t* __restrict__ recs, int64_t ng, int C,
+                                                          HighResultSpec spec) {
+  const int o = blockIdx.y;
+  const int64_t g = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (g >= ng) return;
+  const HighRec r = load_high(recs + (g * C + spec.col[o]) * kHighRecordFields);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const double v = spec.stat[o] == HighStat::SKEWNESS ? sqrt(r.n) * r.m3 / (r.m2 * sqrt(r.m2))
+                                                      : r.n * r.m4 / (r.m2 * r.m2) - 3.0;
+  spec.out[o][g] = (r.n >= 1.0 && r.m2 != 0.0 && r.bad == 0) ? v : nan;
+}
+
 // ------------------------------------------------------------------ host API
 namespace {
 
@@ -610,6 +738,77 @@ void pair_results(const int64_t* records, int64_t ng, int npairs, const PairResu
   hipLaunchKernelGGL(pair_results_kernel, dim3((unsigned)((ng + kT - 1) / kT), spec.n), dim3(kT), 0, s, records, ng,
                      npairs, spec);
   TFA_LAUNCH_CHECK("pair_results_kernel");
+}
+
+// workspace: group_items' (unused when the items are given) | records part[nseg + max_chunks][C]
+size_t group_high_moments_workspace_bytes(int ncols, int64_t nperm, int64_t nseg) {
+  if (nseg <= 0 || ncols <= 0) return 0;
+  const size_t part = static_cast<size_t>(nseg + max_chunks(nperm)) * ncols * (8 * kHighRecordFields);
+  return group_items_workspace_bytes(nseg) + part;
+}
+
+void group_high_moments(const StatCols& cols, int64_t n, const int64_t* perm, int64_t nperm, const int64_t* offsets,
+                        int64_t nseg, int64_t* records, void* ws, size_t ws_size, hipStream_t s,
+                        const GroupItems* given) {
+  TFA_CHECK(cols.n >= 1 && cols.n <= kMaxPackCols, "group_high_moments: 1..", kMaxPackCols, " columns, got ", cols.n);
+  TFA_CHECK(n >= 0 && nperm >= 0 && nperm <= n && nseg >= 0, "group_high_moments: bad row or segment count");
+  check_stat_columns("group_high_moments", cols, n);
+  if (n == 0 || nseg == 0) return;
+  TFA_CHECK(nseg < (int64_t(1) << 31) && nseg + max_chunks(nperm) < (int64_t(1) << 31),
+            "group_high_moments: too many segments");
+  TFA_CHECK(perm != nullptr && offsets != nullptr && records != nullptr && ws != nullptr,
+            "group_high_moments: null buffer");
+  TFA_CHECK(reinterpret_cast<uintptr_t>(records) % 8 == 0 && reinterpret_cast<uintptr_t>(ws) % 8 == 0,
+            "group_high_moments: unaligned buffer");
+  TFA_CHECK(ws_size >= group_high_moments_workspace_bytes(cols.n, nperm, nseg),
+            "group_high_moments: workspace too small");
+  const size_t items_bytes = group_items_workspace_bytes(nseg);
+  const GroupItems it = given ? *given : group_items(offsets, nseg, nperm, ws, items_bytes, s);
+  TFA_CHECK(it.coffs != nullptr && it.items >= nseg && it.items <= nseg + max_chunks(nperm),
+            "group_high_moments: ", it.items, " work items for ", nseg, " segments of ", nperm, " rows");
+  const int64_t items = it.items;
+  int64_t* part = reinterpret_cast<int64_t*>(static_cast<char*>(ws) + items_bytes);
+  const bool single = items == nseg;  // every segment is one chunk: item == segment
+  hipLaunchKernelGGL(group_high_moments_kernel, dim3((unsigned)((items + kWaves - 1) / kWaves), cols.n), dim3(kT), 0,
+                     s, cols, n, perm, nperm, offsets, (const int64_t*)it.coffs, nseg, items,
+                     single ? records : part);
+  TFA_LAUNCH_CHECK("group_high_moments_kernel");
+  if (single) return;
+  hipLaunchKernelGGL(group_high_fold_kernel, dim3((unsigned)((nseg * cols.n + kT - 1) / kT)), dim3(kT), 0, s, cols.n,
+                     (const int64_t*)part, (const int64_t*)it.coffs, nseg, items, records);
+  TFA_LAUNCH_CHECK("group_high_fold_kernel");
+}
+
+void merge_high_records(const int64_t* records, int64_t m, int ncols, const int64_t* offsets, int64_t ng,
+                        int64_t* out, hipStream_t s) {
+  TFA_CHECK(ncols >= 1 && ncols <= kMaxPackCols, "merge_high_records: 1..", kMaxPackCols, " columns, got ", ncols);
+  TFA_CHECK(m >= 0 && ng >= 0, "merge_high_records: negative count");
+  if (ng == 0) return;
+  TFA_CHECK(offsets != nullptr && out != nullptr && (m == 0 || records != nullptr), "merge_high_records: null buffer");
+  TFA_CHECK(ng * ncols < (int64_t(1) << 38), "merge_high_records: too many groups");
+  hipLaunchKernelGGL(merge_high_records_kernel, dim3((unsigned)((ng * ncols + kT - 1) / kT)), dim3(kT), 0, s, records,
+                     m, ncols, offsets, ng, out);
+  TFA_LAUNCH_CHECK("merge_high_records_kernel");
+}
+
+void high_results(const int64_t* records, int64_t ng, int ncols, const HighResultSpec& spec, hipStream_t s) {
+  TFA_CHECK(ncols >= 1 && ncols <= kMaxPackCols, "high_results: 1..", kMaxPackCols, " columns, got ", ncols);
+  TFA_CHECK(spec.n >= 1 && spec.n <= kMaxPackCols, "high_results: 1..", kMaxPackCols, " outputs, got ", spec.n);
+  TFA_CHECK(ng >= 0, "high_results: negative group count");
+  for (int o = 0; o < spec.n; ++o) {
+    TFA_CHECK(spec.col[o] >= 0 && spec.col[o] < ncols, "high_results: output ", o, " names column ", spec.col[o],
+              " of ", ncols);
+    const int st = static_cast<int>(spec.stat[o]);
+    TFA_CHECK(st >= 0 && st <= static_cast<int>(HighStat::KURTOSIS), "high_results: output ", o,
+              " asks for an unknown statistic");
+    TFA_CHECK(ng == 0 || spec.out[o] != nullptr, "high_results: output ", o, " has no buffer");
+  }
+  if (ng == 0) return;
+  TFA_CHECK(records != nullptr, "high_results: null records");
+  TFA_CHECK((ng + kT - 1) / kT < (int64_t(1) << 31), "high_results: too many groups");
+  hipLaunchKernelGGL(high_results_kernel, dim3((unsigned)((ng + kT - 1) / kT), spec.n), dim3(kT), 0, s, records, ng,
+                     ncols, spec);
+  TFA_LAUNCH_CHECK("high_results_kernel");
 }
 
 void merge_group_records(const int64_t* records, int64_t m, int ncols, uint32_t float_mask, const int64_t* offsets,

@@ -346,6 +346,20 @@ constexpr int kPairRecordFields = 7;
 size_t column_pair_moments_workspace_bytes(int npairs, int64_t n);
 void column_pair_moments(const StatCols& xs, const StatCols& ys, int64_t n, int64_t* records, void* workspace,
                          size_t workspace_size, hipStream_t s);
+// one high-moments record per column in one launch pair, for skewness /
+// kurtosis: records[c] = kHighRecordFields int64 bit patterns {n, mean, M2, M3,
+// M4} as f64 (Mk = sum (x - mean)^k, every element converted to f64 first) and
+// the count of rows that are NaN or an infinity. A lane takes runs of 16
+// consecutive rows (16-byte vector loads where the runs are aligned, scalar
+// loads otherwise); a run enters as one batch (its mean and central sums, one
+// Pébay merge), the rows after the last run through Welford's one-row update;
+// lanes, waves and blocks are merged in order: no float atomics, no power sums
+// of x, the same bits on every run, a function of the row count alone. n == 0
+// launches nothing and leaves records alone (the caller fills zeros).
+constexpr int kHighRecordFields = 6;
+size_t column_high_moments_workspace_bytes(int ncols, int64_t n);
+void column_high_moments(const StatCols& cols, int64_t n, int64_t* records, void* workspace, size_t workspace_size,
+                         hipStream_t s);
 // hist[p][d] (device int64 [P][256], overwritten) = rows whose word has its top
 // prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] (host) and whose
 // next 8-bit digit is d; prefix_bits == 0 takes P == 1 and ignores the prefix.
@@ -430,6 +444,33 @@ struct PairResultSpec {
 // rows), corr = C / sqrt(M2_x * M2_y) (NaN without rows or where an M2 is 0;
 // not clamped); all three NaN where the record counts a non-finite row
 void pair_results(const int64_t* records, int64_t ng, int npairs, const PairResultSpec& spec, hipStream_t s);
+// high-moments records [nseg][cols.n][kHighRecordFields] (the stats section)
+// of the same CSR segments and work items: Welford's one-row update per lane
+// over rows gathered through perm, the lanes merged in lane order with Pébay's
+// formulas, a segment's chunks folded in chunk order (a segment of many chunks
+// by a whole wave). A record depends on the segment's rows in row order alone.
+// n == 0 or nseg == 0 launches nothing.
+size_t group_high_moments_workspace_bytes(int ncols, int64_t nperm, int64_t nseg);
+void group_high_moments(const StatCols& cols, int64_t n, const int64_t* perm, int64_t nperm, const int64_t* offsets,
+                        int64_t nseg, int64_t* records, void* workspace, size_t workspace_size, hipStream_t s,
+                        const GroupItems* items = nullptr);
+// out [ng][ncols][6] = high records [m][ncols][6] rows offsets[g] ..
+// offsets[g + 1] merged in order (Pébay; the non-finite counts add), starting
+// from the group's first record; a group without records gets the empty one
+void merge_high_records(const int64_t* records, int64_t m, int ncols, const int64_t* offsets, int64_t ng,
+                        int64_t* out, hipStream_t s);
+enum class HighStat : int { SKEWNESS = 0, KURTOSIS };
+struct HighResultSpec {
+  int n = 0;
+  int col[kMaxPackCols];  // the record column an output reads
+  HighStat stat[kMaxPackCols];
+  double* out[kMaxPackCols];  // [ng]
+};
+// every output column of merged high records [ng][ncols][6] in one launch:
+// skewness = sqrt(n) M3 / M2^1.5, kurtosis = n M4 / M2^2 - 3 (the excess, from
+// population moments); NaN without rows, where M2 is 0 (one row included) and
+// where the record counts a non-finite row
+void high_results(const int64_t* records, int64_t ng, int ncols, const HighResultSpec& spec, hipStream_t s);
 
 // ------------------------------------------------------------ window functions (window_scan.hip)
 // Window / .over(). The n rows of one partition are sorted by (partition

@@ -4,8 +4,10 @@
 // rule it passes as `extra` (merge(r, a, b) and shfl_xor(o, r, off), run
 // between m2 and lo). The record of two columns read together (PairRec, for
 // corr / covar_samp / covar_pop) follows with its own update, merge, shuffle
-// and wave butterfly. The build contracts with -ffp-contract=fast: the shape
-// and order of these expressions decide the bits of every result.
+// and wave butterfly, and after it the record of the third and fourth central
+// moments of one column (HighRec, for skewness / kurtosis). The build contracts
+// with -ffp-contract=fast: the shape and order of these expressions decide the
+// bits of every result.
 #pragma once
 
 #include <cstdint>
@@ -153,6 +155,113 @@ __device__ __forceinline__ PairRec load_pair(const int64_t* __restrict__ src) {
   r.m2y = __longlong_as_double(src[4]);
   r.cxy = __longlong_as_double(src[5]);
   r.bad = static_cast<uint64_t>(src[6]);
+  return r;
+}
+
+// ------------------------------------------------------------------ high moments
+// The record of one column's central moments up to order four (skewness /
+// kurtosis): n, the mean and Mk = sum (x - mean)^k for k = 2, 3, 4 as f64, and
+// the count of rows that are NaN or an infinity (the results are decided from
+// that count, not from what such a row left in the floats). Everything is a
+// sum of powers of deviations from a running mean, updated and merged; a power
+// sum of x itself appears nowhere. The empty record is all zeros.
+struct HighRec {
+  double n, mean, m2, m3, m4;
+  uint64_t bad;
+};
+
+__device__ __forceinline__ HighRec high_empty() { return HighRec{0.0, 0.0, 0.0, 0.0, 0.0, 0ull}; }
+
+// Welford's update with one row in Terriberry's form. With d = x - mean,
+// dn = d / n and t = d * dn * (n - 1) (n the count after the row): m4 first
+// (it reads the old m3 and m2), then m3 (the old m2), then m2, then the mean.
+// Each sum is written term by term, left to right, as below.
+__device__ __forceinline__ void high_add_row(HighRec& r, double x) {
+  const double n1 = r.n;
+  r.n += 1.0;
+  const double n = r.n;
+  const double d = x - r.mean;
+  const double dn = d / n;
+  const double dn2 = dn * dn;
+  const double t = d * dn * n1;
+  r.m4 += t * dn2 * (n * n - 3.0 * n + 3.0) + 6.0 * dn2 * r.m2 - 4.0 * dn * r.m3;
+  r.m3 += t * dn * (n - 2.0) - 3.0 * dn * r.m2;
+  r.m2 += t;
+  r.mean += dn;
+  r.bad += __builtin_isfinite(x) ? 0ull : 1ull;
+}
+
+// Pébay's merge of two records, `a` the earlier rows. delta = mean_b - mean_a,
+// n = na + nb, dn = delta / n. The terms, in the order they are added:
+//   M2 = M2a + M2b + delta^2 na nb / n                  (merge_moments' form)
+//   M3 = M3a + M3b + dn^2 delta na nb (na - nb) + 3 dn (na M2b - nb M2a)
+//   M4 = M4a + M4b + dn^3 delta na nb (na^2 - na nb + nb^2)
+//        + 6 dn^2 (na^2 M2b + nb^2 M2a) + 4 dn (na M3b - nb M3a)
+// with merge_moments' empty-side selects: an empty side is selected away and
+// never mixed in, so merging an empty record changes no bit.
+__device__ __forceinline__ HighRec merge_high(const HighRec& a, const HighRec& b) {
+  HighRec r;
+  r.n = a.n + b.n;
+  const double delta = b.mean - a.mean;
+  const double f = r.n > 0.0 ? b.n / r.n : 0.0;
+  const double dn = r.n > 0.0 ? delta / r.n : 0.0;
+  const double dn2 = dn * dn;
+  const double nab = a.n * b.n;
+  const double mean = a.mean + delta * f;
+  const double m2 = a.m2 + b.m2 + delta * delta * (a.n * f);
+  const double m3 = a.m3 + b.m3 + dn2 * delta * (nab * (a.n - b.n)) + 3.0 * dn * (a.n * b.m2 - b.n * a.m2);
+  const double m4 = a.m4 + b.m4 + dn2 * dn * delta * (nab * (a.n * a.n - nab + b.n * b.n)) +
+                    6.0 * dn2 * (a.n * a.n * b.m2 + b.n * b.n * a.m2) + 4.0 * dn * (a.n * b.m3 - b.n * a.m3);
+  r.mean = a.n == 0.0 ? b.mean : (b.n == 0.0 ? a.mean : mean);
+  r.m2 = a.n == 0.0 ? b.m2 : (b.n == 0.0 ? a.m2 : m2);
+  r.m3 = a.n == 0.0 ? b.m3 : (b.n == 0.0 ? a.m3 : m3);
+  r.m4 = a.n == 0.0 ? b.m4 : (b.n == 0.0 ? a.m4 : m4);
+  r.bad = a.bad + b.bad;
+  return r;
+}
+
+__device__ __forceinline__ HighRec shfl_xor_high(const HighRec& r, int off) {
+  HighRec o;
+  o.n = __shfl_xor(r.n, off, kWave);
+  o.mean = __shfl_xor(r.mean, off, kWave);
+  o.m2 = __shfl_xor(r.m2, off, kWave);
+  o.m3 = __shfl_xor(r.m3, off, kWave);
+  o.m4 = __shfl_xor(r.m4, off, kWave);
+  o.bad = __shfl_xor(static_cast<unsigned long long>(r.bad), off, kWave);
+  return o;
+}
+
+// wave_merge_moments for high records: lane order, neighbours first, the
+// wave's record in lane 0; the steps at or above `rows` are skipped
+__device__ __forceinline__ HighRec wave_merge_high(HighRec r, int64_t rows = kWave) {
+  const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    if (off >= rows) break;
+    const HighRec o = shfl_xor_high(r, off);
+    r = (lane & off) ? merge_high(o, r) : merge_high(r, o);
+  }
+  return r;
+}
+
+// a record as kHighRecordFields int64 bit patterns and back
+__device__ __forceinline__ void store_high(int64_t* __restrict__ dst, const HighRec& r) {
+  dst[0] = __double_as_longlong(r.n);
+  dst[1] = __double_as_longlong(r.mean);
+  dst[2] = __double_as_longlong(r.m2);
+  dst[3] = __double_as_longlong(r.m3);
+  dst[4] = __double_as_longlong(r.m4);
+  dst[5] = static_cast<int64_t>(r.bad);
+}
+
+__device__ __forceinline__ HighRec load_high(const int64_t* __restrict__ src) {
+  HighRec r;
+  r.n = __longlong_as_double(src[0]);
+  r.mean = __longlong_as_double(src[1]);
+  r.m2 = __longlong_as_double(src[2]);
+  r.m3 = __longlong_as_double(src[3]);
+  r.m4 = __longlong_as_double(src[4]);
+  r.bad = static_cast<uint64_t>(src[5]);
   return r;
 }
 

@@ -19,6 +19,13 @@
 //            whose runs are not 16-byte aligned is read with scalar loads), a
 //            run entering as one batch. The result depends on the row count
 //            alone. Nothing is ever computed as sum(xy) - n mean_x mean_y.
+//   high     per column one record {n, mean, M2, M3, M4, rows with a NaN or an
+//            infinity} (moments.h HighRec) for skewness / kurtosis: the
+//            structure of pairs, the column on the grid's y. A lane takes runs
+//            of 16 consecutive rows (whole 16-byte vectors, or scalar loads
+//            where the runs are not aligned), two runs in flight; a run enters
+//            as one batch (its own mean and central sums, one Pébay merge).
+//            Never sum(x^3) or sum(x^4).
 //   hist     one step of a most-significant-digit-first radix select: for up
 //            to kMaxPackCols word prefixes, the 256-bin histogram of the next
 //            8-bit digit over the rows whose word starts with the prefix. The
@@ -374,6 +381,119 @@ __global__ __launch_bounds__(kT) void pair_moments_final_kernel(const PairRec* _
   if (threadIdx.x == 0) store_pair(records + (int64_t)q * kPairRecordFields, r);
 }
 
+// ------------------------------------------------------------------ high moments
+namespace {
+
+// The kRun rows of one run enter together: the run's mean, then the sums of
+// the second, third and fourth powers of the deviations from it (two
+// accumulators each, even and odd rows), then one merge_high with the lane's
+// record: two divisions per run, not one per row. These are the run's own
+// central moments, never power sums of x.
+__device__ __forceinline__ void high_add_run(HighRec& r, const double (&x)[kRun]) {
+  // the run's sum as a pairwise tree, neighbours first: every step of a run of
+  // equal values is exact, so a constant column has M2 == 0 exactly
+  double s[kRun];
+  uint64_t bad = 0;
+#pragma unroll
+  for (int j = 0; j < kRun; ++j) {
+    s[j] = x[j];
+    bad += __builtin_isfinite(x[j]) ? 0ull : 1ull;
+  }
+#pragma unroll
+  for (int w = 1; w < kRun; w <<= 1) {
+#pragma unroll
+    for (int j = 0; j < kRun; j += 2 * w) s[j] += s[j + w];
+  }
+  const double bm = s[0] * (1.0 / kRun);  // (kRun is a power of two)
+  double b2[2] = {0.0, 0.0}, b3[2] = {0.0, 0.0}, b4[2] = {0.0, 0.0};
+#pragma unroll
+  for (int j = 0; j < kRun; ++j) {
+    const double d = x[j] - bm;
+    const double d2 = d * d;
+    b2[j & 1] += d2;
+    b3[j & 1] = fma(d2, d, b3[j & 1]);
+    b4[j & 1] = fma(d2, d2, b4[j & 1]);
+  }
+  r = merge_high(r, HighRec{static_cast<double>(kRun), bm, b2[0] + b2[1], b3[0] + b3[1], b4[0] + b4[1], bad});
+}
+
+// the block's high record in thread 0: lanes in lane order, then the waves in
+// wave order
+__device__ __forceinline__ HighRec block_merge_high(HighRec r, HighRec* lds /*[kWaves]*/) {
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  r = wave_merge_high(r);
+  if (lane == 0) lds[w] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < kWaves; ++i) r = merge_high(r, lds[i]);
+  }
+  return r;
+}
+
+// one lane's record of the runs t, t + kT, ... of rows [lo, lo + nrun * kRun)
+// of one column: two runs are loaded before the first enters (every load of
+// both is in flight together), and they enter in row order
+template <typename T>
+__device__ __forceinline__ HighRec lane_high_runs(const void* __restrict__ src, int64_t lo, int64_t nrun) {
+  const bool vec = run_aligned<T>(src, lo);  // (uniform)
+  HighRec r = high_empty();
+  int64_t j = threadIdx.x;
+  for (; j + kT < nrun; j += 2 * kT) {
+    double x0[kRun], x1[kRun];
+    load_run<T>(src, lo + j * kRun, vec, x0);
+    load_run<T>(src, lo + (j + kT) * kRun, vec, x1);
+    high_add_run(r, x0);
+    high_add_run(r, x1);
+  }
+  if (j < nrun) {
+    double x0[kRun];
+    load_run<T>(src, lo + j * kRun, vec, x0);
+    high_add_run(r, x0);
+  }
+  return r;
+}
+
+}  // namespace
+
+// block (b, c): rows [b * chunk, min(n, (b + 1) * chunk)) of column c ->
+// part[c][b]. chunk is a multiple of kRun. Thread t takes the runs t, t + kT,
+// ...; the rows after the last whole run (fewer than kRun, in the last block
+// alone) go one to a thread, through the one-row update. Whether the runs are
+// read as 16-byte vectors is decided per block from the address of its first
+// row. The order of every operation depends on n and these constants alone.
+__global__ __launch_bounds__(kT) void high_moments_partial_kernel(StatCols cols, int64_t n, int64_t chunk,
+                                                                  HighRec* __restrict__ part) {
+  __shared__ HighRec lds[kWaves];
+  const int c = blockIdx.y;
+  const int64_t first = (int64_t)blockIdx.x * chunk;
+  const int64_t lo = first < n ? first : n;
+  const int64_t hi = lo + chunk < n ? lo + chunk : n;
+  const void* src = cols.ptr[c];
+  const DType dt = cols.dtype[c];
+  const int64_t nrun = (hi - lo) / kRun;
+  // (the dtype is uniform: one scalar branch per block)
+  HighRec r = dispatch_column(dt, [&](auto tag) { return lane_high_runs<decltype(tag)>(src, lo, nrun); });
+  const int64_t t0 = lo + nrun * kRun + threadIdx.x;
+  if (t0 < hi) high_add_row(r, dispatch_column(dt, [&](auto tag) { return load_row<decltype(tag)>(src, t0); }));
+  r = block_merge_high(r, lds);
+  if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = r;
+}
+
+// block c: part[c][0 .. nb) merged in block order -> records[c]
+__global__ __launch_bounds__(kT) void high_moments_final_kernel(const HighRec* __restrict__ part, int nb,
+                                                                int64_t* __restrict__ records) {
+  __shared__ HighRec lds[kWaves];
+  const int c = blockIdx.x;
+  const HighRec* __restrict__ p = part + (int64_t)c * nb;
+  const int per = (nb + kT - 1) / kT;  // consecutive records per thread
+  const int a = threadIdx.x * per, b = a + per < nb ? a + per : nb;
+  HighRec r = high_empty();
+  for (int i = a; i < b; ++i) r = merge_high(r, p[i]);
+  r = block_merge_high(r, lds);
+  if (threadIdx.x == 0) store_high(records + (int64_t)c * kHighRecordFields, r);
+}
+
 namespace {
 
 struct HistPrefixes {
@@ -501,6 +621,33 @@ void column_pair_moments(const StatCols& xs, const StatCols& ys, int64_t n, int6
   TFA_LAUNCH_CHECK("pair_moments_partial_kernel");
   hipLaunchKernelGGL(pair_moments_final_kernel, dim3(xs.n), dim3(kT), 0, s, (const PairRec*)part, nb, records);
   TFA_LAUNCH_CHECK("pair_moments_final_kernel");
+}
+
+size_t column_high_moments_workspace_bytes(int ncols, int64_t n) {
+  if (n <= 0 || ncols <= 0) return 0;
+  int nb;
+  int64_t chunk;
+  moments_grid(n, &nb, &chunk);
+  return radix::align_up(static_cast<size_t>(ncols) * nb * sizeof(HighRec));
+}
+
+void column_high_moments(const StatCols& cols, int64_t n, int64_t* records, void* ws, size_t ws_size, hipStream_t s) {
+  TFA_CHECK(cols.n >= 1 && cols.n <= kMaxPackCols, "column_high_moments: 1..", kMaxPackCols, " columns, got ", cols.n);
+  TFA_CHECK(n >= 0, "column_high_moments: negative row count");
+  check_stat_columns("column_high_moments", cols, n);
+  if (n == 0) return;
+  TFA_CHECK(records != nullptr && ws != nullptr, "column_high_moments: null buffer");
+  TFA_CHECK(reinterpret_cast<uintptr_t>(records) % 8 == 0 && reinterpret_cast<uintptr_t>(ws) % 8 == 0,
+            "column_high_moments: unaligned buffer");
+  TFA_CHECK(ws_size >= column_high_moments_workspace_bytes(cols.n, n), "column_high_moments: workspace too small");
+  int nb;
+  int64_t chunk;
+  moments_grid(n, &nb, &chunk);  // (chunk: a multiple of 16 == kRun)
+  HighRec* part = static_cast<HighRec*>(ws);
+  hipLaunchKernelGGL(high_moments_partial_kernel, dim3(nb, cols.n), dim3(kT), 0, s, cols, n, chunk, part);
+  TFA_LAUNCH_CHECK("high_moments_partial_kernel");
+  hipLaunchKernelGGL(high_moments_final_kernel, dim3(cols.n), dim3(kT), 0, s, (const HighRec*)part, nb, records);
+  TFA_LAUNCH_CHECK("high_moments_final_kernel");
 }
 
 void select_hist(DType dtype, const void* col, int64_t n, const int64_t* prefixes, int P, int prefix_bits,

@@ -455,6 +455,9 @@ class DataFrame:
         if any(isinstance(n, Column) for n in names):
             return self._select_columns(names)
         for n in names:
+            if type(n).__name__ == "HighAggregateExpression":
+                raise TypeError(f"select: {n.output_name} is an aggregate expression; use agg(...) or "
+                                f"groupBy(...).agg(...)")
             if n not in self._schema:
                 raise ValueError(f"Column {n} not found in {self.columns}")
         schema = StructType([self._schema[n] for n in names])

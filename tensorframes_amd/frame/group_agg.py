@@ -9,7 +9,11 @@ columns), seven fields: n, mean_x, mean_y, M2_x, M2_y, the co-moment
 C_xy = sum (x - mean_x)(y - mean_y) (f64) and the integer count of rows whose
 x or y is NaN or an infinity; the empty record is all zeros. Pair records ride
 with the one-column records through both stages (one row per group for the
-all-to-all) and are merged by their own merge.
+all-to-all) and are merged by their own merge. `skewness` and `kurtosis` have
+a third record per (group, value column), six fields: n, mean, M2, M3, M4
+(Mk = sum (x - mean)^k, f64) and the integer count of rows that are NaN or an
+infinity; it rides after the pair records and is merged with Pébay's formulas.
+The other statistics of a mixed call still come from the first record.
 
 * stage 1: every partition is reduced on its own. Keys are factorised by
   `ops/groupby.group_ids` (the grouping of `groupBy(keys).count()`); device
@@ -37,7 +41,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ..functions import FUNCTIONS, AggregateExpression, PairAggregateExpression
+from ..functions import FUNCTIONS, AggregateExpression, HighAggregateExpression, PairAggregateExpression
 from ..parallel import dist
 from ..utils import dtypes as D
 from ._scalar_columns import (_aggregate_dtype, _block_on_device, _decode_sort_word, _ineligible, _scalar_column,
@@ -52,15 +56,24 @@ _KEY_DTYPES = (D.DT_INT32, D.DT_INT64, D.DT_FLOAT, D.DT_DOUBLE)
 _N, _MEAN, _M2, _SUM, _LO, _HI = range(_FIELDS)
 _PFIELDS = 7  # kernels.h kPairRecordFields
 _PN, _PMX, _PMY, _PM2X, _PM2Y, _PC, _PBAD = range(_PFIELDS)
+_HFIELDS = 6  # kernels.h kHighRecordFields
+_HN, _HMEAN, _HM2, _HM3, _HM4, _HBAD = range(_HFIELDS)
 
 
 # ------------------------------------------------------------------ expressions
 class _Spec:
     """One output column: statistic `fn` of value column `column` (None: rows),
-    or pair statistic `fn` of the ordered pair of value columns `pair`."""
+    pair statistic `fn` of the ordered pair of value columns `pair`, or
+    (`high`) skewness / kurtosis of `column`, read from its high record."""
 
-    def __init__(self, fn: str, column: Optional[str], name: str, pair: Optional[Tuple[str, str]] = None):
-        self.fn, self.column, self.name, self.pair = fn, column, name, pair
+    def __init__(self, fn: str, column: Optional[str], name: str, pair: Optional[Tuple[str, str]] = None,
+                 high: bool = False):
+        self.fn, self.column, self.name, self.pair, self.high = fn, column, name, pair, high
+
+    @property
+    def plain(self) -> bool:
+        """read from the six-field record of one column"""
+        return self.pair is None and not self.high
 
 
 def _specs(df, keys: Sequence[str], exprs: Sequence[Any], what: str) -> List[_Spec]:
@@ -89,6 +102,14 @@ def _specs(df, keys: Sequence[str], exprs: Sequence[Any], what: str) -> List[_Sp
                 if err is not None:
                     raise err
             out.append(_Spec(e.fn, None, e.output_name, (e.x, e.y)))
+            continue
+        if isinstance(e, HighAggregateExpression):
+            if e.column not in df.schema:
+                raise ValueError(f"{what}: Column {e.column} not found in {df.columns}")
+            err = _ineligible(df, e.column, what)
+            if err is not None:
+                raise err
+            out.append(_Spec(e.fn, e.column, e.output_name, high=True))
             continue
         if not isinstance(e, AggregateExpression):
             hint = " (Column.sum() and friends reduce the cell of one row; use tfs.functions.sum(name))" \
@@ -338,6 +359,97 @@ def _pair_results(recs: np.ndarray, pairs: Sequence[int], stats: Sequence[str]) 
     return outs
 
 
+# ------------------------------------------------------------------ host high records
+def _host_high_records(vals: Sequence[torch.Tensor], ids: np.ndarray, ng: int) -> np.ndarray:
+    """int64 [ng, C, 6]: the high records of one host partition (every group
+    has rows). Per group two passes in f64: the mean (corrected once, as in
+    `_host_group_records`), then the sums of the second, third and fourth
+    powers of the deviations. Never a power sum of x."""
+    out = np.zeros((ng, len(vals), _HFIELDS), dtype=np.int64)
+    order = np.argsort(ids, kind="stable")
+    counts = np.bincount(ids, minlength=ng).astype(np.int64)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    nf = counts.astype(np.float64)
+    for c, v in enumerate(vals):
+        with np.errstate(all="ignore"):
+            x = v.detach().contiguous().numpy()[order].astype(np.float64)
+            mean = np.add.reduceat(x, starts) / nf
+            mean = mean + np.add.reduceat(x - np.repeat(mean, counts), starts) / nf
+            # (a group of equal values has that value as its mean, exactly: M2 == 0, as on the device)
+            lo, hi = np.minimum.reduceat(x, starts), np.maximum.reduceat(x, starts)
+            mean = np.where(lo == hi, lo, mean)
+            d = x - np.repeat(mean, counts)
+            d2 = d * d
+            f = _f64(out[:, c, :_HBAD])
+            f[:, _HN], f[:, _HMEAN] = nf, mean
+            f[:, _HM2] = np.add.reduceat(d2, starts)
+            f[:, _HM3] = np.add.reduceat(d2 * d, starts)
+            f[:, _HM4] = np.add.reduceat(d2 * d2, starts)
+        out[:, c, _HBAD] = np.add.reduceat((~np.isfinite(x)).astype(np.int64), starts)
+    return out
+
+
+def _high_pebay(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Pébay's merge of high records [s, C, 6], `a` the earlier rows (the
+    arithmetic of kernels/moments.h merge_high, without its contractions)."""
+    r = np.empty_like(a)
+    fa, fb, fr = _f64(a[..., :_HBAD]), _f64(b[..., :_HBAD]), _f64(r[..., :_HBAD])
+    an, bn = fa[..., _HN], fb[..., _HN]
+    a2, b2, a3, b3 = fa[..., _HM2], fb[..., _HM2], fa[..., _HM3], fb[..., _HM3]
+    with np.errstate(all="ignore"):
+        n = an + bn
+        delta = fb[..., _HMEAN] - fa[..., _HMEAN]
+        f = np.where(n > 0, bn / np.where(n > 0, n, 1.0), 0.0)
+        dn = np.where(n > 0, delta / np.where(n > 0, n, 1.0), 0.0)
+        dn2 = dn * dn
+        nab = an * bn
+
+        def pick(j, merged):
+            return np.where(an == 0, fb[..., j], np.where(bn == 0, fa[..., j], merged))
+        fr[..., _HN] = n
+        fr[..., _HMEAN] = pick(_HMEAN, fa[..., _HMEAN] + delta * f)
+        fr[..., _HM2] = pick(_HM2, a2 + b2 + delta * delta * (an * f))
+        fr[..., _HM3] = pick(_HM3, a3 + b3 + dn2 * delta * (nab * (an - bn)) + 3.0 * dn * (an * b2 - bn * a2))
+        fr[..., _HM4] = pick(_HM4, fa[..., _HM4] + fb[..., _HM4] + dn2 * dn * delta * (nab * (an * an - nab + bn * bn))
+                             + 6.0 * dn2 * (an * an * b2 + bn * bn * a2) + 4.0 * dn * (an * b3 - bn * a3))
+    r[..., _HBAD] = a[..., _HBAD] + b[..., _HBAD]
+    return r
+
+
+def _merge_high_records(recs: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+    """`_merge_records` for high records [m, C, 6] (every group has a record)."""
+    recs = np.ascontiguousarray(recs)
+    counts = np.diff(offsets)
+    out = recs[offsets[:-1]].copy()
+    for j in range(1, int(counts.max()) if len(counts) else 0):
+        sel = np.nonzero(counts > j)[0]
+        out[sel] = _high_pebay(out[sel], recs[offsets[sel] + j])
+    return out
+
+
+def _high_results(recs: np.ndarray, cols: Sequence[int], stats: Sequence[str]) -> List[np.ndarray]:
+    """Merged high records [ng, C, 6] -> one float64 column per output (the
+    host form of `_C.high_results`): skewness = sqrt(n) M3 / M2^1.5, kurtosis =
+    n M4 / M2^2 - 3; NaN without rows, where M2 is 0 (one row included) and
+    where the record counts a row with a NaN or an infinity."""
+    outs = []
+    for ci, st in zip(cols, stats):
+        r = np.ascontiguousarray(recs[:, ci, :])
+        f = _f64(r[:, :_HBAD])
+        n, m2 = f[:, _HN], f[:, _HM2]
+        ok = (n >= 1) & (m2 != 0) & (r[:, _HBAD] == 0)
+        s2 = np.where(ok, m2, 1.0)
+        with np.errstate(all="ignore"):
+            if st == "skewness":
+                v = np.sqrt(n) * f[:, _HM3] / (s2 * np.sqrt(s2))
+            elif st == "kurtosis":
+                v = n * f[:, _HM4] / (s2 * s2) - 3.0
+            else:
+                raise ValueError(f"'{st}' is not a high-moment statistic")
+        outs.append(np.asarray(np.where(ok, v, np.nan), dtype=np.float64))
+    return outs
+
+
 # ------------------------------------------------------------------ stage 1
 def _columns_of(specs: Sequence[_Spec], what: str) -> Tuple[List[str], List[Tuple[str, str]]]:
     """(distinct value columns of the one-column outputs, distinct ordered
@@ -348,7 +460,7 @@ def _columns_of(specs: Sequence[_Spec], what: str) -> Tuple[List[str], List[Tupl
         if s.pair is not None:
             if s.pair not in pairs:
                 pairs.append(s.pair)
-        elif s.column is not None and s.column not in vcols:
+        elif s.column is not None and not s.high and s.column not in vcols:
             vcols.append(s.column)
     if len(vcols) > _MAX_COLS:
         raise ValueError(f"{what}: at most {_MAX_COLS} distinct value columns per call, got {len(vcols)}; split the "
@@ -359,12 +471,24 @@ def _columns_of(specs: Sequence[_Spec], what: str) -> Tuple[List[str], List[Tupl
     return vcols, pairs
 
 
+def _high_columns_of(specs: Sequence[_Spec], what: str) -> List[str]:
+    """The distinct value columns of the skewness / kurtosis outputs, in order of first use."""
+    hcols: List[str] = []
+    for s in specs:
+        if s.high and s.column not in hcols:
+            hcols.append(s.column)
+    if len(hcols) > _MAX_COLS:
+        raise ValueError(f"{what}: at most {_MAX_COLS} distinct skewness / kurtosis columns per call, got "
+                         f"{len(hcols)}; split the call and join the results on the keys")
+    return hcols
+
+
 def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_device: bool, what: str,
-                       pairs: Sequence[Tuple[str, str]] = (), single: bool = True):
+                       pairs: Sequence[Tuple[str, str]] = (), single: bool = True, hcols: Sequence[str] = ()):
     """(distinct key columns of the partition, records [ng, C, 6] int64, pair
-    records [ng, Q, 7] int64) of one non-empty partition, on the device or on
-    the host; a kind the call does not need (`single` False, no `pairs`) is
-    None."""
+    records [ng, Q, 7] int64, high records [ng, H, 6] int64) of one non-empty
+    partition, on the device or on the host; a kind the call does not need
+    (`single` False, no `pairs`, no `hcols`) is None."""
     from .. import core, engine
     from .._native import _C
     from ..ops import groupby as G
@@ -375,6 +499,7 @@ def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_d
         vals = [engine.device_full(b.nrows, 0, torch.uint8, dev)]
     xs = [_scalar_column(b, x, what).to(dev) for x, _ in pairs]
     ys = [_scalar_column(b, y, what).to(dev) for _, y in pairs]
+    hs = [_scalar_column(b, h, what).to(dev) for h in hcols]
     if keys:
         K = [b.columns[k] for k in keys]
         if not G.device_keys(K):
@@ -383,11 +508,15 @@ def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_d
         ids, uniq, ng = G.group_ids([k.to(dev).contiguous() for k in K])
     else:
         ids, uniq, ng = engine.device_full(b.nrows, 0, torch.int64, dev), [], 1
-    recs = precs = None
+    recs = precs = hrecs = None
     if on_device:
         perm, offsets = _C.segment_csr(ids, ng)
-        vals, xs, ys = ([v.contiguous() for v in vs] for vs in (vals, xs, ys))
-        if vals and xs:  # (the work items of the segments are built once for both)
+        vals, xs, ys, hs = ([v.contiguous() for v in vs] for vs in (vals, xs, ys, hs))
+        if hs and (vals or xs):  # (the work items of the segments are built once for all)
+            recs, precs, hrecs = _C.group_all_moments(vals, xs, ys, hs, perm, offsets)
+        elif hs:
+            hrecs = _C.group_high_moments(hs, perm, offsets)
+        elif vals and xs:  # (the work items of the segments are built once for both)
             recs, precs = _C.group_both_moments(vals, xs, ys, perm, offsets)
         elif vals:
             recs = _C.group_moments(vals, perm, offsets)
@@ -398,6 +527,8 @@ def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_d
             recs = torch.from_numpy(_host_group_records(vals, ids.numpy(), ng))
         if xs:
             precs = torch.from_numpy(_host_pair_records(xs, ys, ids.numpy(), ng))
+        if hs:
+            hrecs = torch.from_numpy(_host_high_records(hs, ids.numpy(), ng))
     where = "device" if on_device else "host"
     if vals:
         metrics.add(f"group_agg_{where}_partitions")
@@ -405,23 +536,29 @@ def _partition_records(b: Block, keys: Sequence[str], vcols: Sequence[str], on_d
     if xs:
         metrics.add(f"pair_agg_{where}_partitions")
         metrics.add("pair_agg_rows", b.nrows * len(xs))
-    return uniq, recs, precs
+    if hs:
+        metrics.add(f"high_agg_{where}_partitions")
+        metrics.add("high_agg_rows", b.nrows * len(hs))
+    return uniq, recs, precs, hrecs
 
 
-def _needed(keys, vcols, pairs=()):
+def _needed(keys, vcols, pairs=(), hcols=()):
     out = list(keys)
-    for v in list(vcols) + [c for p in pairs for c in p]:
+    for v in list(vcols) + [c for p in pairs for c in p] + list(hcols):
         if v not in out:
             out.append(v)
     return out
 
 
-def _outputs(specs, scol, spair, vdt, merged, pmerged, on_device: bool) -> List[torch.Tensor]:
-    """One column per output from the merged records [ng, C, 6] and pair
-    records [ng, Q, 7], in the order of `specs`."""
+def _outputs(specs, scol, spair, vdt, merged, pmerged, on_device: bool, hmerged=None,
+             hcols: Sequence[str] = ()) -> List[torch.Tensor]:
+    """One column per output from the merged records [ng, C, 6], pair records
+    [ng, Q, 7] and high records [ng, H, 6] (of `hcols`), in the order of
+    `specs`."""
     from .._native import _C
-    one = [i for i, s in enumerate(specs) if s.pair is None]
+    one = [i for i, s in enumerate(specs) if s.plain]
     two = [i for i, s in enumerate(specs) if s.pair is not None]
+    high = [i for i, s in enumerate(specs) if s.high]
     outs: List[Any] = [None] * len(specs)
     for a in range(0, len(one), _MAX_COLS):
         at = one[a:a + _MAX_COLS]
@@ -442,16 +579,25 @@ def _outputs(specs, scol, spair, vdt, merged, pmerged, on_device: bool) -> List[
             got = [torch.from_numpy(np.ascontiguousarray(o)) for o in _pair_results(pmerged.numpy(), prs, fns)]
         for i, o in zip(at, got):
             outs[i] = o
+    for a in range(0, len(high), _MAX_COLS):
+        at = high[a:a + _MAX_COLS]
+        cols, fns = [hcols.index(specs[i].column) for i in at], [specs[i].fn for i in at]
+        if on_device:
+            got = _C.high_results(hmerged.contiguous(), cols, fns)
+        else:
+            got = [torch.from_numpy(np.ascontiguousarray(o)) for o in _high_results(hmerged.numpy(), cols, fns)]
+        for i, o in zip(at, got):
+            outs[i] = o
     return outs
 
 
 # ------------------------------------------------------------------ both stages
 def _merged_records(blocks, keys: Sequence[str], n_route: int, vcols, pairs, single: bool, kdt, is_float,
-                    needed: Sequence[str], what: str):
+                    needed: Sequence[str], what: str, hcols: Sequence[str] = ()):
     """Stage 1 and stage 2 of a keyed aggregate over this rank's partitions:
     (on_device, the distinct key columns [ng] in ascending lexicographic
-    order, merged records [ng, C, 6], merged pair records [ng, Q, 7]) of the
-    keys this rank answers for; a kind the call does not need is None. None
+    order, merged records [ng, C, 6], merged pair records [ng, Q, 7], merged
+    high records [ng, H, 6]) of the keys this rank answers for; a kind the call does not need is None. None
     when no rank has rows, or none arrive here. Collective.
 
     The first `n_route` keys decide the rank of a record (`GroupedData.agg`:
@@ -462,8 +608,9 @@ def _merged_records(blocks, keys: Sequence[str], n_route: int, vcols, pairs, sin
     from .._native import _C
     from ..ops import groupby as G
     C = max(len(vcols), 1) if single else 0
-    Q = len(pairs)
-    W1, W = C * _FIELDS, C * _FIELDS + Q * _PFIELDS  # a group's row: its records, then its pair records
+    Q, H = len(pairs), len(hcols)
+    W1, W2 = C * _FIELDS, C * _FIELDS + Q * _PFIELDS
+    W = W2 + H * _HFIELDS  # a group's row: its records, then its pair records, then its high records
     parts = [(pid, b) for pid, b in sorted(blocks.items()) if b.nrows]
     # decided together, so every rank takes the same (collective) path:
     # the device path when no rank holds a needed column on the host
@@ -476,9 +623,10 @@ def _merged_records(blocks, keys: Sequence[str], n_route: int, vcols, pairs, sin
     dev = engine.compute_device() if on_device else torch.device("cpu")
     got = []
     for pid, b in parts:
-        u, r, pr = _partition_records(b, keys, vcols, on_device, what, pairs, single)
-        ng = int((r if r is not None else pr).shape[0])
-        row = [t.reshape(ng, -1) for t in (r, pr) if t is not None]
+        u, r, pr, hr = _partition_records(b, keys, vcols, on_device, what, pairs, single, hcols)
+        row = [t for t in (r, pr, hr) if t is not None]
+        ng = int(row[0].shape[0])
+        row = [t.reshape(ng, -1) for t in row]
         got.append((pid, u, row[0] if len(row) == 1 else torch.cat(row, dim=1)))
     if got:
         K = [engine.cat_rows([u[j] for _, u, _ in got]) for j in range(len(keys))]
@@ -490,13 +638,15 @@ def _merged_records(blocks, keys: Sequence[str], n_route: int, vcols, pairs, sin
         pids = engine.device_empty(0, torch.int64, dev)
 
     def split(rows):
-        """rows [m, W] -> (records [m, C, 6], pair records [m, Q, 7]); a kind without columns is None"""
+        """rows [m, W] -> (records [m, C, 6], pair records [m, Q, 7], high records [m, H, 6]); a kind
+        without columns is None"""
         m = int(rows.shape[0])
         return (rows[:, :W1].contiguous().reshape(m, C, _FIELDS) if C else None,
-                rows[:, W1:].contiguous().reshape(m, Q, _PFIELDS) if Q else None)
+                rows[:, W1:W2].contiguous().reshape(m, Q, _PFIELDS) if Q else None,
+                rows[:, W2:].contiguous().reshape(m, H, _HFIELDS) if H else None)
     if not dist.is_distributed() and len(got) == 1:
-        merged, pmerged = split(R)  # one partition: its records are the result
-        return on_device, K, merged, pmerged
+        merged, pmerged, hmerged = split(R)  # one partition: its records are the result
+        return on_device, K, merged, pmerged, hmerged
     if dist.is_distributed():
         recv = G.route(K[:n_route], K[n_route:] + [pids, R])
         K, pids, R = recv[:len(keys)], recv[len(keys)], recv[len(keys) + 1]
@@ -514,21 +664,25 @@ def _merged_records(blocks, keys: Sequence[str], n_route: int, vcols, pairs, sin
     else:
         ordered[ids] = R
     ids2, ukeys, ng = G.group_ids([u.contiguous() for u in uniq[:-1]])
-    recs, precs = split(ordered)
-    merged = pmerged = None
+    recs, precs, hrecs = split(ordered)
+    merged = pmerged = hmerged = None
     if on_device:
         _, offsets = _C.segment_csr(ids2, ng)
         if C:
             merged = _C.merge_group_records(recs, offsets, is_float)
         if Q:
             pmerged = _C.merge_pair_records(precs, offsets)
+        if H:
+            hmerged = _C.merge_high_records(hrecs, offsets)
     else:
         offsets = np.concatenate([[0], np.cumsum(np.bincount(ids2.numpy(), minlength=ng))]).astype(np.int64)
         if C:
             merged = torch.from_numpy(_merge_records(recs.numpy(), offsets, is_float))
         if Q:
             pmerged = torch.from_numpy(_merge_pair_records(precs.numpy(), offsets))
-    return on_device, ukeys, merged, pmerged
+        if H:
+            hmerged = torch.from_numpy(_merge_high_records(hrecs.numpy(), offsets))
+    return on_device, ukeys, merged, pmerged, hmerged
 
 
 # ------------------------------------------------------------------ keyed
@@ -544,14 +698,15 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
         return frame_agg(df, specs, what)
     _check_keys(df, keys, what)
     vcols, pairs = _columns_of(specs, what)
-    single = any(s.pair is None for s in specs)
+    hcols = _high_columns_of(specs, what)
+    single = any(s.plain for s in specs)
     vdt = ([D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]) if single else []
     is_float = [t.is_floating_point for t in vdt]
     kdt = [D.torch_dtype(_tf_dtype(df, k)) for k in keys]
-    out_dt = [torch.float64 if s.pair is not None else _aggregate_dtype(df, s.fn, s.column) for s in specs]
-    scol = [vcols.index(s.column) if s.column is not None else 0 for s in specs]
+    out_dt = [_aggregate_dtype(df, s.fn, s.column) if s.plain else torch.float64 for s in specs]
+    scol = [vcols.index(s.column) if s.plain and s.column is not None else 0 for s in specs]
     spair = [pairs.index(s.pair) if s.pair is not None else 0 for s in specs]
-    needed = _needed(keys, vcols, pairs)
+    needed = _needed(keys, vcols, pairs, hcols)
     keep_on_device = any(b.columns[n].is_cuda for b in (df._cached or {}).values() if b.nrows for n in needed
                          if isinstance(b.columns[n], torch.Tensor))
     world = max(1, dist.world_size())
@@ -562,12 +717,12 @@ def group_agg(grouped, exprs: Sequence[Any], what: str = "agg"):
         return {p: Block(0, dict(cols)) for p in dist.local_partitions(world)}
 
     def compute(blocks):
-        got = _merged_records(blocks, keys, len(keys), vcols, pairs, single, kdt, is_float, needed, what)
+        got = _merged_records(blocks, keys, len(keys), vcols, pairs, single, kdt, is_float, needed, what, hcols)
         if got is None:
             return empty()
-        on_device, ukeys, merged, pmerged = got
-        ng = int((merged if merged is not None else pmerged).shape[0])
-        outs = _outputs(specs, scol, spair, vdt, merged, pmerged, on_device)
+        on_device, ukeys, merged, pmerged, hmerged = got
+        ng = int(next(t for t in (merged, pmerged, hmerged) if t is not None).shape[0])
+        outs = _outputs(specs, scol, spair, vdt, merged, pmerged, on_device, hmerged, hcols)
         keep = on_device and keep_on_device
         cols: Dict[str, Any] = {k: (u if keep else u.cpu()) for k, u in zip(keys, ukeys)}
         cols.update({s.name: (o if keep else o.cpu()) for s, o in zip(specs, outs)})
@@ -588,13 +743,15 @@ def frame_agg(df, specs, what: str = "agg"):
     if not isinstance(specs, list) or not all(isinstance(s, _Spec) for s in specs):
         specs = _specs(df, [], list(specs), what)
     vcols, pairs = _columns_of(specs, what)
-    single = any(s.pair is None for s in specs)
+    hcols = _high_columns_of(specs, what)
+    single = any(s.plain for s in specs)
     C = max(len(vcols), 1) if single else 0
-    Q = len(pairs)
-    W1, W = C * _FIELDS, C * _FIELDS + Q * _PFIELDS
+    Q, H = len(pairs), len(hcols)
+    W1, W2 = C * _FIELDS, C * _FIELDS + Q * _PFIELDS
+    W = W2 + H * _HFIELDS
     vdt = ([D.torch_dtype(_tf_dtype(df, v)) for v in vcols] or [torch.uint8]) if single else []
     is_float = [t.is_floating_point for t in vdt]
-    scol = [vcols.index(s.column) if s.column is not None else 0 for s in specs]
+    scol = [vcols.index(s.column) if s.plain and s.column is not None else 0 for s in specs]
     spair = [pairs.index(s.pair) if s.pair is not None else 0 for s in specs]
     pcols = _needed([], [], pairs)
 
@@ -603,7 +760,7 @@ def frame_agg(df, specs, what: str = "agg"):
         from .._native import _C
         from ..utils.logging import metrics
         blocks = df._blocks()
-        # a partition's row: its records [C, 6], then its pair records [Q, 7]
+        # a partition's row: its records [C, 6], then its pair records [Q, 7], then its high records [H, 6]
         table = torch.zeros((df.num_partitions, W), dtype=torch.int64)
         for pid in sorted(blocks):
             b = blocks[pid]
@@ -612,39 +769,51 @@ def frame_agg(df, specs, what: str = "agg"):
             if single:
                 on_device = engine.gpu_available() and _block_on_device(b, vcols) and bool(vcols)
                 table[pid, :W1] = _partition_records(b, [], vcols, on_device, what)[1].cpu()[0].reshape(-1)
+            if H and engine.gpu_available() and _block_on_device(b, hcols):
+                # read where it is, densely: no CSR of one segment, no gather
+                hs = [_scalar_column(b, h, what).contiguous() for h in hcols]
+                table[pid, W2:] = _C.column_high_moments(hs).cpu().reshape(-1)
+                metrics.add("high_agg_device_partitions")
+                metrics.add("high_agg_rows", b.nrows * H)
+            elif H:
+                table[pid, W2:] = _partition_records(b, [], [], False, what, (), False, hcols)[3][0].reshape(-1)
             if not Q:
                 continue
             if engine.gpu_available() and _block_on_device(b, pcols):
                 # read where it is, densely: no CSR of one segment, no gather
                 xs = [_scalar_column(b, x, what).contiguous() for x, _ in pairs]
                 ys = [_scalar_column(b, y, what).contiguous() for _, y in pairs]
-                table[pid, W1:] = _C.column_pair_moments(xs, ys).cpu().reshape(-1)
+                table[pid, W1:W2] = _C.column_pair_moments(xs, ys).cpu().reshape(-1)
                 metrics.add("pair_agg_device_partitions")
                 metrics.add("pair_agg_rows", b.nrows * Q)
             else:
-                table[pid, W1:] = _partition_records(b, [], [], False, what, pairs, False)[2][0].reshape(-1)
+                table[pid, W1:W2] = _partition_records(b, [], [], False, what, pairs, False)[2][0].reshape(-1)
         dist.all_reduce_host_(table, "Sum")  # (every rank fills the rows of its own partitions; the others are zero)
         return table.numpy()
     table = np.ascontiguousarray(dist.agreed(what, run))
-    # the partitions with rows, in partition order (n is the first field of both record kinds)
+    # the partitions with rows, in partition order (n is the first field of every record kind)
     table = table[_f64(np.ascontiguousarray(table[:, 0])) > 0]
     recs = np.ascontiguousarray(table[:, :W1]).reshape(-1, C, _FIELDS) if C else None
-    precs = np.ascontiguousarray(table[:, W1:]).reshape(-1, Q, _PFIELDS) if Q else None
-    merged = pmerged = None
+    precs = np.ascontiguousarray(table[:, W1:W2]).reshape(-1, Q, _PFIELDS) if Q else None
+    hrecs = np.ascontiguousarray(table[:, W2:]).reshape(-1, H, _HFIELDS) if H else None
+    merged = pmerged = hmerged = None
     if len(table):
         whole = np.array([0, len(table)], dtype=np.int64)
         if C:
             merged = _merge_records(recs, whole, is_float)
         if Q:
             pmerged = _merge_pair_records(precs, whole)
+        if H:
+            hmerged = _merge_high_records(hrecs, whole)
     else:
         for s in specs:
             if s.fn in ("min", "max"):
                 raise ValueError(f"{what}: {s.fn}({s.column}) of a frame without rows does not exist")
         merged = np.zeros((1, C, _FIELDS), dtype=np.int64) if C else None
         pmerged = np.zeros((1, Q, _PFIELDS), dtype=np.int64) if Q else None
+        hmerged = np.zeros((1, H, _HFIELDS), dtype=np.int64) if H else None
     outs = _outputs(specs, scol, spair, vdt, torch.from_numpy(merged) if C else None,
-                    torch.from_numpy(pmerged) if Q else None, False)
+                    torch.from_numpy(pmerged) if Q else None, False, torch.from_numpy(hmerged) if H else None, hcols)
     return from_columns({s.name: np.ascontiguousarray(o.numpy()) for s, o in zip(specs, outs)}, num_partitions=1)
 
 

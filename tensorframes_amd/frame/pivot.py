@@ -27,7 +27,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ..functions import FUNCTIONS, AggregateExpression
+from ..functions import FUNCTIONS, AggregateExpression, HighAggregateExpression
 from ..parallel import dist
 from ..utils import dtypes as D
 from ._scalar_columns import _aggregate_dtype, _stat_columns, _tf_dtype
@@ -270,6 +270,9 @@ def pivot_agg(pivoted: PivotedData, exprs: Sequence[Any], what: str):
     from .window import refuse_window_expression
     df, keys, pcol, values = pivoted.df, pivoted.keys, pivoted.pivot_col, pivoted.values
     refuse_window_expression(what, exprs)
+    if any(isinstance(e, HighAggregateExpression) for e in exprs):
+        raise NotImplementedError(f"{what}: skewness and kurtosis are not supported under pivot; use "
+                                  f"groupBy({', '.join(keys + [pcol])}).agg(...) and reshape its result")
     if has_order_aggregates(exprs):
         raise NotImplementedError(f"{what}: order aggregates (median, percentile, percentile_approx, mode, "
                                   f"countDistinct) are not supported under pivot; use groupBy({', '.join(keys + [pcol])})"
@@ -319,7 +322,7 @@ def pivot_agg(pivoted: PivotedData, exprs: Sequence[Any], what: str):
         got = _merged_records(blocks, all_keys, len(keys), vcols, pairs, single, kdt, is_float, needed, what)
         if got is None:
             return empty()
-        on_device, ukeys, merged, pmerged = got
+        on_device, ukeys, merged, pmerged, _ = got
         metrics.add(f"pivot_{'device' if on_device else 'host'}_partitions", nparts)
         outs = _outputs(specs, scol, spair, vdt, merged, pmerged, on_device)
         gkeys, G, wide = _spread(on_device, list(ukeys[:-1]), ukeys[-1], value_words, outs, fills)

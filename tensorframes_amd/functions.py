@@ -6,7 +6,9 @@
 Each function takes a column name or a plain column reference (`tfs.col("x")`,
 `df["x"]`) and returns an `AggregateExpression`; `.alias(name)` renames its
 output column. `corr`, `covar_samp` and `covar_pop` take two columns and return
-a `PairAggregateExpression`, accepted wherever the others are. `median`,
+a `PairAggregateExpression`, `skewness` and `kurtosis` take one column and
+return a `HighAggregateExpression`; both are accepted wherever the others are
+in `agg`, but not in its dict form. `median`,
 `percentile`, `percentile_approx`, `mode`, `countDistinct` and
 `approx_count_distinct` need a group's rows in order and return an
 `OrderAggregateExpression`, accepted in `agg` as well (frame/order_agg.py);
@@ -24,7 +26,7 @@ from .frame.column import Column
 __all__ = ["AggregateExpression", "PairAggregateExpression", "OrderAggregateExpression", "median", "percentile",
            "percentile_approx", "mode", "countDistinct", "count_distinct", "approx_count_distinct", "count", "sum", "avg", "mean", "min", "max", "stddev",
            "stddev_samp", "stddev_pop", "variance", "var_samp", "var_pop", "corr", "covar_samp", "covar_pop",
-           "row_number", "rank", "dense_rank", "rand", "randn"]
+           "HighAggregateExpression", "skewness", "kurtosis", "row_number", "rank", "dense_rank", "rand", "randn"]
 
 # the canonical statistic behind every accepted name (the dict form of agg uses the same table)
 FUNCTIONS = {
@@ -104,6 +106,37 @@ class PairAggregateExpression:
 
     def __repr__(self):
         return f"PairAggregateExpression<{self.output_name}>"
+
+
+class HighAggregateExpression:
+    """One aggregate of one column's third or fourth central moment: `fn` is
+    skewness or kurtosis, `column` the value column's name. The output is
+    float64."""
+
+    __slots__ = ("fn", "column", "_alias")
+
+    def __init__(self, fn: str, column: str, alias: Optional[str] = None):
+        self.fn = fn
+        self.column = column
+        self._alias = alias
+
+    def alias(self, name: str) -> "HighAggregateExpression":
+        if not isinstance(name, str) or not name:
+            raise TypeError(f"alias: a non-empty column name is expected, got {name!r}")
+        return HighAggregateExpression(self.fn, self.column, name)
+
+    name = alias
+
+    @property
+    def output_name(self) -> str:
+        return self._alias if self._alias is not None else f"{self.fn}({self.column})"
+
+    def over(self, spec):
+        raise NotImplementedError(f"{self.fn}({self.column}).over: high-moment aggregates are not supported over a "
+                                  f"window; count, sum, avg, min and max are")
+
+    def __repr__(self):
+        return f"HighAggregateExpression<{self.output_name}>"
 
 
 _MAX_PERCENTAGES = 16  # kernels.h kMaxPercentages
@@ -258,6 +291,19 @@ def covar_samp(col1, col2) -> PairAggregateExpression:
 def covar_pop(col1, col2) -> PairAggregateExpression:
     """The population covariance C / n."""
     return _make_pair("covar_pop", col1, col2)
+
+
+def skewness(col) -> HighAggregateExpression:
+    """sqrt(n) M3 / M2^1.5 with Mk = sum (x - mean)^k over the group's rows as
+    float64 (Spark's skewness): NaN for a group without rows or with a constant
+    column (one row included), and for a group with a NaN or an infinity."""
+    return HighAggregateExpression("skewness", _make("skewness", col).column)
+
+
+def kurtosis(col) -> HighAggregateExpression:
+    """The excess kurtosis from population moments, n M4 / M2^2 - 3 (Spark's
+    kurtosis); NaN where `skewness` is."""
+    return HighAggregateExpression("kurtosis", _make("kurtosis", col).column)
 
 
 def _percentages(fn: str, percentage):
