@@ -1461,6 +1461,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "up to 16 dense scalar device columns [n] (mixed dtypes, contiguous) -> int64 records [C, 6] (bit patterns): n, "
      "mean, M2, M3, M4 (Mk = sum (x - mean)^k) as f64 and the count of rows that are NaN or an infinity; the same "
      "bits on every run. n == 0 launches nothing and gives empty records (all zeros)");
+  m.def("vector_moments", [](const at::Tensor& x, const py::object& slice_rows) {
+    const char* what = "vector_moments";
+    if (!x.is_cuda()) throw py::value_error(str_cat(what, ": x must be a device tensor"));
+    if (x.dim() != 2) throw py::value_error(str_cat(what, ": x must be 2-D (one vector [d] per row), got ", x.dim(), "-D"));
+    if (x.scalar_type() != at::kFloat && x.scalar_type() != at::kDouble)
+      throw py::type_error(str_cat(what, ": x is ", c10::toString(x.scalar_type()), ", which is not supported (float32 "
+                                   "or float64)"));
+    if (!x.is_contiguous()) throw py::value_error(str_cat(what, ": x is not contiguous; make it contiguous first"));
+    const int64_t n = x.size(0), d = x.size(1);
+    if (d < 1 || d > k::kVectorMomentsMaxD)
+      throw py::value_error(str_cat(what, ": cells of 1..", k::kVectorMomentsMaxD, " components expected, got ", d));
+    int64_t forced = 0;
+    if (!slice_rows.is_none()) {
+      if (!py::isinstance<py::int_>(slice_rows) || py::isinstance<py::bool_>(slice_rows))
+        throw py::type_error(str_cat(what, ": slice_rows must be an int or None"));
+      forced = slice_rows.cast<int64_t>();
+      if (forced < 1) throw py::value_error(str_cat(what, ": slice_rows must be positive, got ", forced));
+    }
+    const auto f64 = x.options().dtype(at::kDouble);
+    if (n == 0) return std::make_pair(at::zeros({d}, f64), at::zeros({d, d}, f64));  // nothing is launched
+    const k::VectorMomentsPlan plan = k::vector_moments_plan(n, static_cast<int>(d), forced);
+    c10::hip::HIPGuard guard(x.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+    at::Tensor mean = pool_empty({d}, f64), C = pool_empty({d, d}, f64);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((plan.workspace_bytes + 7) / 8)}, f64);
+    k::vector_moments(x.data_ptr(), from_scalar_type(x.scalar_type()), n, static_cast<int>(d), plan,
+                      mean.data_ptr<double>(), C.data_ptr<double>(), ws.data_ptr(),
+                      static_cast<size_t>(ws.numel()) * 8, s);
+    return std::make_pair(mean, C);
+  }, py::arg("x"), py::arg("slice_rows") = py::none(),
+     "x [n, d] (float32 or float64, contiguous, on the device, 1 <= d <= 512) -> (mean f64 [d], C f64 [d, d]) with C = "
+     "sum_r (x_r - mean)(x_r - mean)^T, exactly symmetric: column sums, a centred SYRK on the f64 MFMA over tile pairs "
+     "x row slices, a fold in slice order; the same bits on every run. A component with a NaN or an infinity has a NaN "
+     "row and column. slice_rows (a multiple of 32) forces the rows per slice; None chooses it from (n, d). n == 0 "
+     "launches nothing and gives zeros");
   // the CSR of a grouped call: perm [n] and offsets [nseg + 1] on the columns' device; returns nseg
   auto group_csr = [group_index](const char* what, const at::Tensor& perm, const at::Tensor& offsets,
                                  const at::Device& dev, int64_t n) {

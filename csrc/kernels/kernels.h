@@ -360,6 +360,29 @@ constexpr int kHighRecordFields = 6;
 size_t column_high_moments_workspace_bytes(int ncols, int64_t n);
 void column_high_moments(const StatCols& cols, int64_t n, int64_t* records, void* workspace, size_t workspace_size,
                          hipStream_t s);
+// ---- vector columns (vector_moments.hip): Correlation.corr / Correlation.cov
+// mean [d] and C [d][d] = sum_r (x_r - mean)(x_r - mean)^T (both f64, C exactly
+// symmetric) of x [n][d], row-major f32 or f64, aligned to the element, n >= 1,
+// 1 <= d <= kVectorMomentsMaxD. Three launches: chunked column sums, a centred
+// SYRK on v_mfma_f64_16x16x4_f64 over (tile pair bi <= bj) x (row slice), and a
+// fold of the slice partials in slice order. A component that holds a NaN or
+// an infinity gets a NaN row and column; the others are untouched. No float
+// atomics: the bits depend on (n, d, slice_rows) alone.
+constexpr int kVectorMomentsMaxD = 512;
+struct VectorMomentsPlan {
+  int tiles = 0, pairs = 0;       // 64-feature tiles; tile pairs bi <= bj
+  int64_t slice_rows = 0, slices = 0;
+  int lpr_log2 = 0;               // the means pass: log2 of the lanes across a row
+  int64_t mean_chunk_rows = 0;
+  int mean_chunks = 0;
+  size_t workspace_bytes = 0;
+};
+// slice_rows <= 0: chosen from (n, d) so that the grid fills the device about
+// twice; otherwise a multiple of 32 that leaves the workspace under 1 GB
+// (GraphError if not)
+VectorMomentsPlan vector_moments_plan(int64_t n, int d, int64_t slice_rows);
+void vector_moments(const void* x, DType dtype, int64_t n, int d, const VectorMomentsPlan& plan, double* mean,
+                    double* C, void* workspace, size_t workspace_size, hipStream_t s);
 // hist[p][d] (device int64 [P][256], overwritten) = rows whose word has its top
 // prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] (host) and whose
 // next 8-bit digit is d; prefix_bits == 0 takes P == 1 and ignores the prefix.

@@ -37,6 +37,21 @@ HIP_FLAGS = [
     "-Wno-unused-result",
 ]
 
+# Per-file additions to HIP_FLAGS. vector_moments.hip alone is compiled with
+# the packed-f32 VALU forms of gfx950 switched off (the target feature
+# packed-fp32-ops). Its only f32 work is the staging of four-wide f32 quads
+# (loads, zero fills, conversion to f64), which is what the vectoriser would
+# pack if it ever found arithmetic there, and its outputs are specified bit
+# for bit against a reference that assumes one IEEE operation per element.
+# Checked on the gfx950 ISA (--save-temps): with the flag there is no v_pk_*_f32
+# instruction, no scratch, and the same 128 MFMAs; today's compiler emits no
+# packed f32 without the flag either, so the flag is a guard, not a fix, and
+# costs nothing (vm_syrk<float>: 74 VGPRs with it, 76 without). The figures in
+# docs/PERFORMANCE.md and the recorded profile are from this compile line.
+HIP_FILE_FLAGS = {
+    "vector_moments.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
+
 HIP_SOURCES = sorted(glob.glob(os.path.join(HERE, "csrc", "kernels", "*.hip")))
 HIP_HEADERS = sorted(glob.glob(os.path.join(HERE, "csrc", "kernels", "*.h"))) + [
     os.path.join(HERE, "csrc", "common.h")
@@ -56,7 +71,8 @@ def compile_hip_objects(jobs=None):
         obj = _hip_object(src)
         if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_mtime):
             return obj
-        cmd = [os.path.join(ROCM, "bin", "hipcc"), *HIP_FLAGS, "-I", os.path.join(HERE, "csrc"),
+        cmd = [os.path.join(ROCM, "bin", "hipcc"), *HIP_FLAGS, *HIP_FILE_FLAGS.get(os.path.basename(src), []),
+               "-I", os.path.join(HERE, "csrc"),
                "-c", src, "-o", obj]
         print("[hipcc]", os.path.basename(src), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
