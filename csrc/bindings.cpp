@@ -1496,6 +1496,50 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "x row slices, a fold in slice order; the same bits on every run. A component with a NaN or an infinity has a NaN "
      "row and column. slice_rows (a multiple of 32) forces the rows per slice; None chooses it from (n, d). n == 0 "
      "launches nothing and gives zeros");
+  m.def("vector_summary", [](const at::Tensor& x, const py::object& w, const py::object& slice_rows) {
+    const char* what = "vector_summary";
+    if (!x.is_cuda()) throw py::value_error(str_cat(what, ": x must be a device tensor"));
+    if (x.dim() != 2) throw py::value_error(str_cat(what, ": x must be 2-D (one vector [d] per row), got ", x.dim(), "-D"));
+    if (x.scalar_type() != at::kFloat && x.scalar_type() != at::kDouble)
+      throw py::type_error(str_cat(what, ": x is ", c10::toString(x.scalar_type()), ", which is not supported (float32 "
+                                   "or float64)"));
+    if (!x.is_contiguous()) throw py::value_error(str_cat(what, ": x is not contiguous; make it contiguous first"));
+    const int64_t n = x.size(0), d = x.size(1);
+    if (n < 1) throw py::value_error(str_cat(what, ": at least one row expected"));
+    if (d < 1 || d > k::kVectorSummaryMaxD)
+      throw py::value_error(str_cat(what, ": cells of 1..", k::kVectorSummaryMaxD, " components expected, got ", d));
+    at::Tensor wt;  // (kept alive until the launches are queued)
+    DType wdtype = DType::F64;
+    const void* wptr = nullptr;
+    if (!w.is_none()) {
+      wt = w.cast<at::Tensor>();
+      stat_column_like(what, wt, "w", "x", x.device(), n, &wdtype, &wptr);
+    }
+    int64_t forced = 0;
+    if (!slice_rows.is_none()) {
+      if (!py::isinstance<py::int_>(slice_rows) || py::isinstance<py::bool_>(slice_rows))
+        throw py::type_error(str_cat(what, ": slice_rows must be an int or None"));
+      forced = slice_rows.cast<int64_t>();
+      if (forced < 1) throw py::value_error(str_cat(what, ": slice_rows must be positive, got ", forced));
+    }
+    const k::VectorSummaryPlan plan = k::vector_summary_plan(n, static_cast<int>(d), forced);
+    c10::hip::HIPGuard guard(x.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+    const auto i64 = x.options().dtype(at::kLong);
+    at::Tensor rec = pool_empty({k::kVectorSummaryHeader + k::kVectorSummaryFields * d}, i64);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((plan.workspace_bytes + 7) / 8)}, i64);
+    k::vector_summary(x.data_ptr(), from_scalar_type(x.scalar_type()), wptr, wdtype, n, static_cast<int>(d), plan,
+                      rec.data_ptr<int64_t>(), ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    return rec;
+  }, py::arg("x"), py::arg("w") = py::none(), py::arg("slice_rows") = py::none(),
+     "x [n, d] (float32 or float64, contiguous, on the device, n >= 1, 1 <= d <= 65536) and optional weights w [n] (one "
+     "of the seven statistics dtypes; None: every weight 1.0) -> int64 bit patterns [4 + 8 d]: the header {rows of "
+     "positive weight, W = sum w, Q = sum w^2, weights that are negative, NaN or infinite}, then eight fields [8][d]: "
+     "the weighted mean, M2 = sum w (x - mean)^2, sum w |x|, sum w x^2 (f64), the counts of entries != 0 and of "
+     "entries that are NaN or an infinity, the smallest and largest sort word of the values as f64. One read of x: "
+     "weighted Welford per thread, Chan merges across row lanes and slices in a fixed order; the same bits on every "
+     "run, and for a 4-byte-aligned view as for an aligned copy. Rows of weight 0 are skipped. slice_rows forces the "
+     "rows per slice; None chooses it from (n, d)");
   // the CSR of a grouped call: perm [n] and offsets [nseg + 1] on the columns' device; returns nseg
   auto group_csr = [group_index](const char* what, const at::Tensor& perm, const at::Tensor& offsets,
                                  const at::Device& dev, int64_t n) {

@@ -383,6 +383,35 @@ struct VectorMomentsPlan {
 VectorMomentsPlan vector_moments_plan(int64_t n, int d, int64_t slice_rows);
 void vector_moments(const void* x, DType dtype, int64_t n, int d, const VectorMomentsPlan& plan, double* mean,
                     double* C, void* workspace, size_t workspace_size, hipStream_t s);
+// ---- vector columns (vector_summary.hip): Summarizer
+// The weighted per-component summary of x [n][d], row-major f32 or f64, aligned
+// to the element, n >= 1, 1 <= d <= kVectorSummaryMaxD; w (may be null: every
+// weight 1.0) is [n] of one of the seven statistics dtypes. One read of x gives
+// the record: kVectorSummaryHeader int64 words {rows of positive weight, W =
+// sum w, Q = sum w^2 (f64 bits), weights that are negative, NaN or infinite},
+// then kVectorSummaryFields fields [field][d]: the weighted mean, M2 = sum w (x
+// - mean)^2, sum w |x|, sum w x^2 (f64 bits), the counts of entries != 0 and of
+// entries that are NaN or an infinity, the smallest and the largest sort word
+// of the values as f64. Rows of weight 0 and rows of a bad weight are skipped.
+// Two launches: per (256 components) x (row slice) a weighted Welford walk and
+// a fixed tree of Chan merges through LDS, then a fold in slice order. No float
+// atomics: the bits depend on (n, d, slice_rows) alone.
+constexpr int kVectorSummaryMaxD = 65536;
+constexpr int kVectorSummaryHeader = 4;
+constexpr int kVectorSummaryFields = 8;
+struct VectorSummaryPlan {
+  int groups = 0;                 // groups of 256 components
+  int lpr_log2 = 0;               // log2 of the lanes across a row
+  int64_t slice_rows = 0, slices = 0;
+  size_t workspace_bytes = 0;
+};
+// slice_rows <= 0: chosen from (n, d) so that the grid fills the device about
+// twice; otherwise any positive row count that leaves the workspace under 1 GB
+// (GraphError if not)
+VectorSummaryPlan vector_summary_plan(int64_t n, int d, int64_t slice_rows);
+void vector_summary(const void* x, DType dtype, const void* w, DType wdtype, int64_t n, int d,
+                    const VectorSummaryPlan& plan, int64_t* record, void* workspace, size_t workspace_size,
+                    hipStream_t s);
 // hist[p][d] (device int64 [P][256], overwritten) = rows whose word has its top
 // prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] (host) and whose
 // next 8-bit digit is d; prefix_bits == 0 takes P == 1 and ignores the prefix.

@@ -5,7 +5,8 @@
 // between m2 and lo). The record of two columns read together (PairRec, for
 // corr / covar_samp / covar_pop) follows with its own update, merge, shuffle
 // and wave butterfly, and after it the record of the third and fourth central
-// moments of one column (HighRec, for skewness / kurtosis). The build contracts
+// moments of one column (HighRec, for skewness / kurtosis), and last the
+// per-component record of a weighted vector summary (SumRec). The build contracts
 // with -ffp-contract=fast: the shape and order of these expressions decide the
 // bits of every result.
 #pragma once
@@ -13,6 +14,7 @@
 #include <cstdint>
 
 #include "hip_common.h"
+#include "sort_words.h"
 
 namespace tfa {
 namespace k {
@@ -262,6 +264,63 @@ __device__ __forceinline__ HighRec load_high(const int64_t* __restrict__ src) {
   r.m3 = __longlong_as_double(src[3]);
   r.m4 = __longlong_as_double(src[4]);
   r.bad = static_cast<uint64_t>(src[5]);
+  return r;
+}
+
+// ------------------------------------------------------------------ weighted summary
+// One component's record of the weighted summary of a vector column
+// (Summarizer, vector_summary.hip): the weighted mean, M2 = sum w (x - mean)^2,
+// L1 = sum w |x| and S2 = sum w x^2 as f64, the counts of entries that are not
+// zero and of entries that are NaN or an infinity, and the smallest and largest
+// ascending sort word of the values as f64. What belongs to a row rather than
+// to a component (the weight sum W, sum w^2, the row count) is carried once by
+// the caller for all the components it owns. Contraction is off in the two
+// functions below and the fused operations are written out: their bits do not
+// depend on the caller. The empty record is zeros, all ones in lo.
+struct SumRec {
+  double mean, m2, l1, s2;
+  uint64_t nnz, bad, lo, hi;
+};
+
+__device__ __forceinline__ SumRec summary_empty() { return SumRec{0.0, 0.0, 0.0, 0.0, 0ull, 0ull, ~0ull, 0ull}; }
+
+// West's update with one row of weight w > 0; f = w / (W + w) with W the weight
+// sum before the row (the caller forms it once per row)
+__device__ __forceinline__ void summary_add_row(SumRec& r, double x, double w, double f) {
+#pragma clang fp contract(off)
+  const double delta = x - r.mean;
+  r.mean = __builtin_fma(delta, f, r.mean);
+  r.m2 = __builtin_fma(w * delta, x - r.mean, r.m2);
+  r.l1 = __builtin_fma(w, __builtin_fabs(x), r.l1);
+  r.s2 = __builtin_fma(w * x, x, r.s2);
+  r.nnz += x != 0.0 ? 1ull : 0ull;  // (-0.0 is zero, a NaN is not)
+  r.bad += __builtin_isfinite(x) ? 0ull : 1ull;
+  const uint64_t word = encode_f64(static_cast<uint64_t>(__double_as_longlong(x)));
+  r.lo = word < r.lo ? word : r.lo;
+  r.hi = word > r.hi ? word : r.hi;
+}
+
+// the factor of Chan's weighted merge: the later side's share of the weight
+__device__ __forceinline__ double summary_fraction(double wa, double wb) {
+  const double w = wa + wb;
+  return w > 0.0 ? wb / w : 0.0;
+}
+
+// Chan's merge of two records of weight sums wa and wb, `a` the earlier side,
+// f = summary_fraction(wa, wb): merge_moments' factor order and empty-side
+// selects with weight sums in the counts' place
+__device__ __forceinline__ SumRec merge_summary(double wa, const SumRec& a, double wb, const SumRec& b, double f) {
+#pragma clang fp contract(off)
+  SumRec r;
+  const double delta = b.mean - a.mean;
+  r.mean = wa == 0.0 ? b.mean : (wb == 0.0 ? a.mean : a.mean + delta * f);
+  r.m2 = wa == 0.0 ? b.m2 : (wb == 0.0 ? a.m2 : a.m2 + b.m2 + delta * delta * (wa * f));
+  r.l1 = a.l1 + b.l1;
+  r.s2 = a.s2 + b.s2;
+  r.nnz = a.nnz + b.nnz;
+  r.bad = a.bad + b.bad;
+  r.lo = a.lo < b.lo ? a.lo : b.lo;
+  r.hi = a.hi > b.hi ? a.hi : b.hi;
   return r;
 }
 

@@ -446,8 +446,13 @@ class DataFrame:
         """Columns by name or `Column` expressions, mixed. A plain reference
         (aliased or not) is zero-copy: the same tensor under the new name, the
         field copied with all of its metadata. Computed expressions of one
-        select run as ONE map_blocks over a generated graph."""
+        select run as ONE map_blocks over a generated graph. A call made of
+        `Summarizer` expressions (`tensorframes_amd.ml.stat`) alone gives a
+        lazy frame of one row, one column per metric."""
         names = [c for cs in cols for c in (cs if isinstance(cs, (list, tuple)) else [cs])]
+        if any(type(n).__name__ == "SummaryExpression" for n in names):
+            from ..ml.stat import summary_frame
+            return summary_frame(self, names, "select")
         if any(isinstance(n, RandomExpression) for n in names):
             return self._select_randoms(names)
         if any(isinstance(n, WindowExpression) for n in names):
@@ -846,8 +851,14 @@ class DataFrame:
         as F, or `agg({"x": "sum"})`. One row, in one partition, identical on
         every rank; names, types and values as in `GroupedData.agg`. A frame
         without rows gives count 0, sum 0 and NaN for avg, stddev and variance;
-        a `min` or `max` of it raises ValueError. An action, and collective."""
+        a `min` or `max` of it raises ValueError. An action, and collective.
+        A call made of `Summarizer` expressions (`tensorframes_amd.ml.stat`)
+        alone gives the lazy one-row frame of `select` with them."""
         from .group_agg import group_agg
+        flat = [e for es in exprs for e in (es if isinstance(es, (list, tuple)) else [es])]
+        if any(type(e).__name__ == "SummaryExpression" for e in flat):
+            from ..ml.stat import summary_frame
+            return summary_frame(self, flat, "agg")
         return group_agg(GroupedData(self, []), list(exprs))
 
     def corr(self, col1, col2, method="pearson") -> float:

@@ -1,1 +1,1 @@
-"""Counterparts of `pyspark.ml`: `tensorframes_amd.ml.stat.Correlation`."""
+"""Counterparts of `pyspark.ml`: `tensorframes_amd.ml.stat.Correlation` and `tensorframes_amd.ml.stat.Summarizer`."""
