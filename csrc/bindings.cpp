@@ -1540,6 +1540,97 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "weighted Welford per thread, Chan merges across row lanes and slices in a fixed order; the same bits on every "
      "run, and for a 4-byte-aligned view as for an aligned copy. Rows of weight 0 are skipped. slice_rows forces the "
      "rows per slice; None chooses it from (n, d)");
+  // kmeans_step / kmeans_assign: the checked arguments, the shift (the mean of the centres: plain f64 sums over
+  // k in index order on the host, then / k) and the centres and the shift on x's device
+  struct KMeansArgs {
+    int64_t n, d, k;
+    at::Tensor centers, shift;  // device, f64
+  };
+  auto kmeans_args = [](const char* what, const at::Tensor& x, const at::Tensor& centers) {
+    if (!x.is_cuda()) throw py::value_error(str_cat(what, ": x must be a device tensor"));
+    if (x.dim() != 2) throw py::value_error(str_cat(what, ": x must be 2-D (one vector [d] per row), got ", x.dim(), "-D"));
+    if (x.scalar_type() != at::kFloat && x.scalar_type() != at::kDouble)
+      throw py::type_error(str_cat(what, ": x is ", c10::toString(x.scalar_type()), ", which is not supported (float32 "
+                                   "or float64)"));
+    if (!x.is_contiguous()) throw py::value_error(str_cat(what, ": x is not contiguous; make it contiguous first"));
+    if (centers.dim() != 2) throw py::value_error(str_cat(what, ": centers must be 2-D [k, d], got ", centers.dim(), "-D"));
+    if (centers.scalar_type() != at::kDouble)
+      throw py::type_error(str_cat(what, ": centers are ", c10::toString(centers.scalar_type()), ", float64 expected"));
+    if (centers.is_cuda() && centers.device() != x.device())
+      throw py::value_error(str_cat(what, ": centers are on another device than x"));
+    KMeansArgs a;
+    a.n = x.size(0), a.d = x.size(1), a.k = centers.size(0);
+    if (a.n < 1) throw py::value_error(str_cat(what, ": at least one row expected"));
+    if (centers.size(1) != a.d)
+      throw py::value_error(str_cat(what, ": x has cells of ", a.d, " components, the centres of ", centers.size(1)));
+    if (a.d < 1 || a.d > k::kKMeansMaxD || a.k < 1 || a.k > k::kKMeansMaxK || a.k * a.d > k::kKMeansMaxKD)
+      throw py::value_error(str_cat(what, ": 1 <= d <= ", k::kKMeansMaxD, ", 1 <= k <= ", k::kKMeansMaxK, " and k d <= ",
+                                    k::kKMeansMaxKD, " expected, got d = ", a.d, ", k = ", a.k));
+    const at::Tensor host = centers.cpu().contiguous();
+    const double* c = host.data_ptr<double>();
+    at::Tensor shift = at::empty({a.d}, at::TensorOptions().dtype(at::kDouble));
+    double* o = shift.data_ptr<double>();
+    for (int64_t f = 0; f < a.d; ++f) {
+      double t = 0.0;
+      for (int64_t j = 0; j < a.k; ++j) t += c[j * a.d + f];
+      o[f] = t / static_cast<double>(a.k);
+      if (!std::isfinite(o[f])) throw py::value_error(str_cat(what, ": the centres hold a NaN or an infinity"));
+    }
+    a.centers = centers.is_cuda() ? centers.contiguous() : host.to(x.device());
+    a.shift = shift.to(x.device());
+    return a;
+  };
+  m.def("kmeans_step", [kmeans_args](const at::Tensor& x, const at::Tensor& centers, const py::object& slice_rows) {
+    const char* what = "kmeans_step";
+    const KMeansArgs a = kmeans_args(what, x, centers);
+    int64_t forced = 0;
+    if (!slice_rows.is_none()) {
+      if (!py::isinstance<py::int_>(slice_rows) || py::isinstance<py::bool_>(slice_rows))
+        throw py::type_error(str_cat(what, ": slice_rows must be an int or None"));
+      forced = slice_rows.cast<int64_t>();
+      if (forced < 1 || forced % k::kKMeansStage)
+        throw py::value_error(str_cat(what, ": slice_rows must be a positive multiple of ", k::kKMeansStage, ", got ",
+                                      forced));
+    }
+    const int d = static_cast<int>(a.d), kk = static_cast<int>(a.k);
+    const k::KMeansPlan plan = k::kmeans_plan(a.n, d, kk, forced);
+    c10::hip::HIPGuard guard(x.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+    const auto f64 = x.options().dtype(at::kDouble), i64 = x.options().dtype(at::kLong);
+    at::Tensor counts = pool_empty({a.k}, i64), sums = pool_empty({a.k, a.d}, f64), cost = pool_empty({1}, f64),
+               bad = pool_empty({1}, i64);
+    at::Tensor assign = pool_empty({a.n}, x.options().dtype(at::kInt)), dist = pool_empty({a.n}, f64);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((plan.workspace_bytes + 7) / 8)}, f64);
+    k::kmeans_step(x.data_ptr(), from_scalar_type(x.scalar_type()), a.n, d, kk, a.centers.data_ptr<double>(),
+                   a.shift.data_ptr<double>(), plan, assign.data_ptr<int32_t>(), dist.data_ptr<double>(),
+                   counts.data_ptr<int64_t>(), sums.data_ptr<double>(), cost.data_ptr<double>(),
+                   bad.data_ptr<int64_t>(), ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    return py::make_tuple(counts, sums, cost, bad);
+  }, py::arg("x"), py::arg("centers"), py::arg("slice_rows") = py::none(),
+     "one Lloyd step: x [n, d] (float32 or float64, contiguous, on the device, n >= 1) and centers [k, d] (float64, on "
+     "x's device or on the host; 1 <= k <= 1024, 1 <= d <= 2048, k d <= 262144, all finite) -> (counts int64 [k], sums "
+     "f64 [k, d], cost f64 [1], bad int64 [1]). Both operands are shifted by shift = the mean of the centres (f64 on "
+     "the host: added over k in index order, then / k): a row goes to the centre of the smallest ||c'||^2 - 2 x'.c' on the f64 "
+     "MFMA (ties to the smallest index; no [n, k] matrix is written), sums are the per-centre sums of x - shift (a "
+     "one-hot GEMM over row slices, folded in slice order), cost is the sum of the squared distances, bad the rows "
+     "that hold a NaN or an infinity (they are in no centre's count or sum). The same bits on every run. slice_rows (a "
+     "multiple of 32) forces the rows per slice; None chooses it from (n, d, k)");
+  m.def("kmeans_assign", [kmeans_args](const at::Tensor& x, const at::Tensor& centers) {
+    const KMeansArgs a = kmeans_args("kmeans_assign", x, centers);
+    const int d = static_cast<int>(a.d), kk = static_cast<int>(a.k);
+    const k::KMeansPlan plan = k::kmeans_plan(a.n, d, kk, /*slice_rows=*/int64_t(1) << 40);  // (no slice partials)
+    c10::hip::HIPGuard guard(x.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+    const auto f64 = x.options().dtype(at::kDouble);
+    at::Tensor assign = pool_empty({a.n}, x.options().dtype(at::kInt)), dist = pool_empty({a.n}, f64);
+    at::Tensor ws = pool_empty({static_cast<int64_t>((plan.workspace_bytes + 7) / 8)}, f64);
+    k::kmeans_assign(x.data_ptr(), from_scalar_type(x.scalar_type()), a.n, d, kk, a.centers.data_ptr<double>(),
+                     a.shift.data_ptr<double>(), plan, assign.data_ptr<int32_t>(), dist.data_ptr<double>(),
+                     ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    return std::make_pair(assign, dist);
+  }, py::arg("x"), py::arg("centers"),
+     "the assignment of kmeans_step alone: (assign int32 [n], dist f64 [n]); -1 and 0.0 for a row that holds a NaN or "
+     "an infinity, otherwise the index of the nearest centre (ties to the smallest) and the squared distance to it");
   // the CSR of a grouped call: perm [n] and offsets [nseg + 1] on the columns' device; returns nseg
   auto group_csr = [group_index](const char* what, const at::Tensor& perm, const at::Tensor& offsets,
                                  const at::Device& dev, int64_t n) {

@@ -412,6 +412,44 @@ VectorSummaryPlan vector_summary_plan(int64_t n, int d, int64_t slice_rows);
 void vector_summary(const void* x, DType dtype, const void* w, DType wdtype, int64_t n, int d,
                     const VectorSummaryPlan& plan, int64_t* record, void* workspace, size_t workspace_size,
                     hipStream_t s);
+// ---- vector columns (kmeans.hip): ml.clustering.KMeans
+// One Lloyd step over x [n][d], row-major f32 or f64, aligned to the element,
+// against centers [k][d] (f64, device), n >= 1, 1 <= k <= kKMeansMaxK, 1 <= d <=
+// kKMeansMaxD, k d <= kKMeansMaxKD. Both operands are shifted by shift [d] (f64,
+// device; the caller's mean of the centres): x' = x - shift, c' = c - shift.
+//   kmeans_assign  a prologue (c' and ||c'||^2 into the workspace) and km_assign:
+//                  per row the centre of the smallest ||c'||^2 - 2 x'.c' (f64
+//                  MFMA, no [n][k] matrix; ties to the smallest index), assign
+//                  [n] int32 (-1 for a row that holds a NaN or an infinity) and
+//                  dist [n] = max(||x'||^2 + best, 0) (0 for a -1 row), and per
+//                  block of 64 rows the sum of dist and the count of -1 rows.
+//   kmeans_step    kmeans_assign, then km_update (per-centre sums of x' as a
+//                  one-hot GEMM over (centre tile) x (feature tile) x (row
+//                  slice), and the rows per centre) and km_finish (folds in
+//                  slice and block order): counts [k] int64, sums [k][d] f64,
+//                  cost [1] f64 = sum dist, bad [1] int64 = -1 rows.
+// No float atomics, no block waits for another one: the bits depend on (n, d,
+// k, slice_rows) alone.
+constexpr int kKMeansMaxK = 1024;
+constexpr int kKMeansMaxD = 2048;
+constexpr int kKMeansMaxKD = 262144;
+constexpr int kKMeansStage = 32;  // rows per stage of km_update: slice_rows is a multiple
+struct KMeansPlan {
+  int ctiles = 0, ftiles = 0;      // 64-centre tiles, 64-feature tiles
+  int64_t blocks = 0;              // km_assign: stripes of 64 rows
+  int64_t slice_rows = 0, slices = 0;
+  size_t workspace_bytes = 0;
+};
+// slice_rows <= 0: chosen from (n, d, k) so that km_update's grid fills the
+// device about twice; otherwise a multiple of 32 that leaves the workspace
+// under 1 GB (GraphError if not)
+KMeansPlan kmeans_plan(int64_t n, int d, int k, int64_t slice_rows);
+void kmeans_assign(const void* x, DType dtype, int64_t n, int d, int k, const double* centers, const double* shift,
+                   const KMeansPlan& plan, int32_t* assign, double* dist, void* workspace, size_t workspace_size,
+                   hipStream_t s);
+void kmeans_step(const void* x, DType dtype, int64_t n, int d, int k, const double* centers, const double* shift,
+                 const KMeansPlan& plan, int32_t* assign, double* dist, int64_t* counts, double* sums, double* cost,
+                 int64_t* bad, void* workspace, size_t workspace_size, hipStream_t s);
 // hist[p][d] (device int64 [P][256], overwritten) = rows whose word has its top
 // prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] (host) and whose
 // next 8-bit digit is d; prefix_bits == 0 takes P == 1 and ignores the prefix.
