@@ -1631,6 +1631,113 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("x"), py::arg("centers"),
      "the assignment of kmeans_step alone: (assign int32 [n], dist f64 [n]); -1 and 0.0 for a row that holds a NaN or "
      "an infinity, otherwise the index of the nearest centre (ties to the smallest) and the squared distance to it");
+  // logreg_step / logreg_predict: the checked arguments and the coefficients on x's device
+  struct LogRegArgs {
+    int64_t n, d, R;
+    at::Tensor coef, icpt;  // device, f64, contiguous
+  };
+  auto logreg_args = [](const char* what, const at::Tensor& x, const at::Tensor& coef, const at::Tensor& icpt,
+                        bool binomial) {
+    if (!x.is_cuda()) throw py::value_error(str_cat(what, ": x must be a device tensor"));
+    if (x.dim() != 2) throw py::value_error(str_cat(what, ": x must be 2-D (one vector [d] per row), got ", x.dim(), "-D"));
+    if (x.scalar_type() != at::kFloat && x.scalar_type() != at::kDouble)
+      throw py::type_error(str_cat(what, ": x is ", c10::toString(x.scalar_type()), ", which is not supported (float32 "
+                                   "or float64)"));
+    if (!x.is_contiguous()) throw py::value_error(str_cat(what, ": x is not contiguous; make it contiguous first"));
+    if (coef.dim() != 2 || icpt.dim() != 1)
+      throw py::value_error(str_cat(what, ": coef [R, d] and icpt [R] expected, got ", coef.dim(), "-D and ", icpt.dim(),
+                                    "-D"));
+    if (coef.scalar_type() != at::kDouble || icpt.scalar_type() != at::kDouble)
+      throw py::type_error(str_cat(what, ": coef and icpt must be float64"));
+    for (const at::Tensor* t : {&coef, &icpt})
+      if (t->is_cuda() && t->device() != x.device())
+        throw py::value_error(str_cat(what, ": coef and icpt must be on x's device or on the host"));
+    LogRegArgs a;
+    a.n = x.size(0), a.d = x.size(1), a.R = coef.size(0);
+    if (a.n < 1) throw py::value_error(str_cat(what, ": at least one row expected"));
+    if (coef.size(1) != a.d || icpt.size(0) != a.R)
+      throw py::value_error(str_cat(what, ": x has cells of ", a.d, " components, coef is [", a.R, ", ", coef.size(1),
+                                    "] and icpt [", icpt.size(0), "]"));
+    if (binomial ? a.R != 1 : (a.R < 2 || a.R > k::kLogRegMaxK))
+      throw py::value_error(str_cat(what, ": a binomial model has R = 1 row of coefficients, a multinomial one R = K in "
+                                    "2..", k::kLogRegMaxK, ", got R = ", a.R));
+    if (a.d < 1 || a.d > k::kLogRegMaxD || a.R * a.d > k::kLogRegMaxRD)
+      throw py::value_error(str_cat(what, ": 1 <= d <= ", k::kLogRegMaxD, " and R d <= ", k::kLogRegMaxRD,
+                                    " expected, got d = ", a.d, ", R = ", a.R));
+    a.coef = coef.to(x.device()).contiguous();
+    a.icpt = icpt.to(x.device()).contiguous();
+    return a;
+  };
+  m.def("logreg_step", [logreg_args](const at::Tensor& x, const at::Tensor& y, const py::object& w,
+                                     const at::Tensor& coef, const at::Tensor& icpt, bool binomial,
+                                     const py::object& slice_rows) {
+    const char* what = "logreg_step";
+    const LogRegArgs a = logreg_args(what, x, coef, icpt, binomial);
+    DType ydtype = DType::F64, wdtype = DType::F64;
+    const void* yptr = nullptr;
+    const void* wptr = nullptr;
+    stat_column_like(what, y, "y", "x", x.device(), a.n, &ydtype, &yptr);
+    at::Tensor wt;  // (kept alive until the launches are queued)
+    if (!w.is_none()) {
+      wt = w.cast<at::Tensor>();
+      stat_column_like(what, wt, "w", "x", x.device(), a.n, &wdtype, &wptr);
+    }
+    int64_t forced = 0;
+    if (!slice_rows.is_none()) {
+      if (!py::isinstance<py::int_>(slice_rows) || py::isinstance<py::bool_>(slice_rows))
+        throw py::type_error(str_cat(what, ": slice_rows must be an int or None"));
+      forced = slice_rows.cast<int64_t>();
+      if (forced < 1 || forced % k::kLogRegStage)
+        throw py::value_error(str_cat(what, ": slice_rows must be a positive multiple of ", k::kLogRegStage, ", got ",
+                                      forced));
+    }
+    const int d = static_cast<int>(a.d), R = static_cast<int>(a.R);
+    const k::LogRegPlan plan = k::logreg_plan(a.n, d, R, forced);
+    c10::hip::HIPGuard guard(x.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+    const auto f64 = x.options().dtype(at::kDouble);
+    at::Tensor loss = pool_empty({1}, f64), grad = pool_empty({a.R, a.d + 1}, f64), wsum = pool_empty({1}, f64),
+               bad = pool_empty({3}, x.options().dtype(at::kLong));
+    at::Tensor ws = pool_empty({static_cast<int64_t>((plan.workspace_bytes + 7) / 8)}, f64);
+    k::logreg_step(x.data_ptr(), from_scalar_type(x.scalar_type()), yptr, ydtype, wptr, wdtype, a.n, d, R,
+                   a.coef.data_ptr<double>(), a.icpt.data_ptr<double>(), plan, loss.data_ptr<double>(),
+                   grad.data_ptr<double>(), wsum.data_ptr<double>(), bad.data_ptr<int64_t>(), ws.data_ptr(),
+                   static_cast<size_t>(ws.numel()) * 8, s);
+    return py::make_tuple(loss, grad, wsum, bad);
+  }, py::arg("x"), py::arg("y"), py::arg("w"), py::arg("coef"), py::arg("icpt"), py::arg("binomial"),
+     py::arg("slice_rows") = py::none(),
+     "one objective evaluation of logistic regression: x [n, d] (float32 or float64, contiguous, on the device, n >= 1), "
+     "labels y [n] and weights w [n] or None (each one of the seven statistics dtypes, on x's device), coef [R, d] and "
+     "icpt [R] (float64, on x's device or on the host; binomial: R = 1, K = 2; multinomial: R = K in 2..128; 1 <= d <= "
+     "4096, R d <= 262144) -> (loss f64 [1], grad f64 [R, d + 1], wsum f64 [1], bad int64 [3]). The margins of a stripe "
+     "of 64 rows stay in f64 MFMA accumulators; loss = sum w (logsumexp(m) - m_y) (binomial: the softplus form without "
+     "a threshold), grad = q^T [x, 1] with q = w (p - onehot(y)) as a dense GEMM over row slices folded in slice order "
+     "(the last column is the intercept's), wsum the sum of the weights of the rows used, bad the rows left out for a "
+     "NaN or an infinity in x, for a label that is no integer in [0, K) and for a negative, NaN or infinite weight (a "
+     "row is counted once, in that order). The same bits on every run. slice_rows (a multiple of 32) forces the rows "
+     "per slice; None chooses it from (n, d, R)");
+  m.def("logreg_predict", [logreg_args](const at::Tensor& x, const at::Tensor& coef, const at::Tensor& icpt,
+                                        bool binomial, double threshold) {
+    const char* what = "logreg_predict";
+    const LogRegArgs a = logreg_args(what, x, coef, icpt, binomial);
+    if (!(threshold >= 0.0 && threshold <= 1.0))
+      throw py::value_error(str_cat(what, ": a threshold in [0, 1] expected, got ", threshold));
+    const int64_t K = binomial ? 2 : a.R;
+    c10::hip::HIPGuard guard(x.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+    const auto f64 = x.options().dtype(at::kDouble);
+    at::Tensor pred = pool_empty({a.n}, x.options().dtype(at::kInt)), raw = pool_empty({a.n, K}, f64),
+               prob = pool_empty({a.n, K}, f64);
+    k::logreg_predict(x.data_ptr(), from_scalar_type(x.scalar_type()), a.n, static_cast<int>(a.d),
+                      static_cast<int>(a.R), a.coef.data_ptr<double>(), a.icpt.data_ptr<double>(),
+                      std::log(threshold / (1.0 - threshold)), pred.data_ptr<int32_t>(), raw.data_ptr<double>(),
+                      prob.data_ptr<double>(), s);
+    return py::make_tuple(pred, raw, prob);
+  }, py::arg("x"), py::arg("coef"), py::arg("icpt"), py::arg("binomial"), py::arg("threshold") = 0.5,
+     "the forward pass of logreg_step in prediction mode: (pred int32 [n], raw f64 [n, K], prob f64 [n, K]); raw are the "
+     "margins (binomial: [-m, m]), prob their softmax (binomial: [sigma(-m), sigma(m)]), pred the first largest "
+     "probability (binomial: m > log(threshold / (1 - threshold))); -1 and zeros for a row of x that holds a NaN or an "
+     "infinity");
   // the CSR of a grouped call: perm [n] and offsets [nseg + 1] on the columns' device; returns nseg
   auto group_csr = [group_index](const char* what, const at::Tensor& perm, const at::Tensor& offsets,
                                  const at::Device& dev, int64_t n) {

@@ -450,6 +450,50 @@ void kmeans_assign(const void* x, DType dtype, int64_t n, int d, int k, const do
 void kmeans_step(const void* x, DType dtype, int64_t n, int d, int k, const double* centers, const double* shift,
                  const KMeansPlan& plan, int32_t* assign, double* dist, int64_t* counts, double* sums, double* cost,
                  int64_t* bad, void* workspace, size_t workspace_size, hipStream_t s);
+// ---- vector columns (logreg.hip): ml.classification.LogisticRegression
+// One objective evaluation over x [n][d], row-major f32 or f64, aligned to the
+// element, with labels y [n] and weights w [n] (w may be null: every weight
+// 1.0), each of one of the seven statistics dtypes, against coef [R][d] and
+// icpt [R] (f64, device). R = 1 is the binomial model (K = 2), R = K >= 2 the
+// multinomial one; n >= 1, 1 <= d <= kLogRegMaxD, K <= kLogRegMaxK, R d <=
+// kLogRegMaxRD.
+//   logreg_step     lr_forward (the margins of a stripe of 64 rows for every
+//                   class in f64 MFMA accumulators, never written; a safe
+//                   softmax / softplus row epilogue; q [n][R] = w (p - onehot
+//                   y) to the workspace; per block its loss, weight sum and
+//                   counts of left-out rows), lr_gradient (q^T [x, 1] as a dense
+//                   GEMM over (class tile) x (feature tile) x (row slice)) and
+//                   lr_finish (folds in slice and block order): loss [1] = sum
+//                   w (logsumexp m - m_y), grad [R][d + 1] (last column: the
+//                   intercept), wsum [1], bad [3] int64 = rows left out for x
+//                   (a NaN or an infinity), y (no integer in [0, K)) and w
+//                   (negative, NaN or infinite), a row counted once.
+//   logreg_predict  lr_forward alone in prediction mode: raw [n][K] (binomial:
+//                   [-m, m]), prob [n][K], pred [n] int32 (the first largest
+//                   probability; binomial: m > logit_threshold); -1 and zeros
+//                   for a row of x with a NaN or an infinity.
+// No float atomics, no block waits for another one: the bits depend on (n, d,
+// R, slice_rows) alone.
+constexpr int kLogRegMaxD = 4096;
+constexpr int kLogRegMaxK = 128;
+constexpr int kLogRegMaxRD = 262144;
+constexpr int kLogRegStage = 32;  // rows per stage of lr_gradient: slice_rows is a multiple
+struct LogRegPlan {
+  int ctiles = 0, ftiles = 0;      // lr_gradient: class tiles and feature tiles
+  int wm = 0;                      // lr_gradient: 1 = 32 classes x 128 features a block, 2 = 64 x 64
+  int64_t blocks = 0;              // lr_forward: stripes of 64 rows
+  int64_t slice_rows = 0, slices = 0;
+  size_t workspace_bytes = 0;
+};
+// slice_rows <= 0: chosen from (n, d, R) so that lr_gradient's grid fills the
+// device about twice; otherwise a multiple of 32 that leaves the workspace
+// under 2 GB (GraphError if not)
+LogRegPlan logreg_plan(int64_t n, int d, int R, int64_t slice_rows);
+void logreg_step(const void* x, DType dtype, const void* y, DType ydtype, const void* w, DType wdtype, int64_t n,
+                 int d, int R, const double* coef, const double* icpt, const LogRegPlan& plan, double* loss,
+                 double* grad, double* wsum, int64_t* bad, void* workspace, size_t workspace_size, hipStream_t s);
+void logreg_predict(const void* x, DType dtype, int64_t n, int d, int R, const double* coef, const double* icpt,
+                    double logit_threshold, int32_t* pred, double* raw, double* prob, hipStream_t s);
 // hist[p][d] (device int64 [P][256], overwritten) = rows whose word has its top
 // prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] (host) and whose
 // next 8-bit digit is d; prefix_bits == 0 takes P == 1 and ignores the prefix.

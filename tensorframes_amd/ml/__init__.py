@@ -1,3 +1,3 @@
-"""Counterparts of `pyspark.ml`: `tensorframes_amd.ml.stat.Correlation`, `tensorframes_amd.ml.stat.Summarizer` and
-`tensorframes_amd.ml.clustering.KMeans`."""
-from . import clustering, stat  # noqa: F401
+"""Counterparts of `pyspark.ml`: `tensorframes_amd.ml.stat.Correlation`, `tensorframes_amd.ml.stat.Summarizer`,
+`tensorframes_amd.ml.clustering.KMeans` and `tensorframes_amd.ml.classification.LogisticRegression`."""
+from . import classification, clustering, stat  # noqa: F401
