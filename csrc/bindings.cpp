@@ -1738,6 +1738,95 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "margins (binomial: [-m, m]), prob their softmax (binomial: [sigma(-m), sigma(m)]), pred the first largest "
      "probability (binomial: m > log(threshold / (1 - threshold))); -1 and zeros for a row of x that holds a NaN or an "
      "infinity");
+  // gmm_step / gmm_predict: the checked arguments and the parameters on x's device
+  struct GmmArgs {
+    int64_t n, d, k;
+    at::Tensor means, transforms, logconst;  // device, f64, contiguous
+  };
+  auto gmm_args = [](const char* what, const at::Tensor& x, const at::Tensor& means, const at::Tensor& transforms,
+                     const at::Tensor& logconst) {
+    if (!x.is_cuda()) throw py::value_error(str_cat(what, ": x must be a device tensor"));
+    if (x.dim() != 2) throw py::value_error(str_cat(what, ": x must be 2-D (one vector [d] per row), got ", x.dim(), "-D"));
+    if (x.scalar_type() != at::kFloat && x.scalar_type() != at::kDouble)
+      throw py::type_error(str_cat(what, ": x is ", c10::toString(x.scalar_type()), ", which is not supported (float32 "
+                                   "or float64)"));
+    if (!x.is_contiguous()) throw py::value_error(str_cat(what, ": x is not contiguous; make it contiguous first"));
+    if (means.dim() != 2 || transforms.dim() != 3 || logconst.dim() != 1)
+      throw py::value_error(str_cat(what, ": means [k, d], transforms [k, d, d] and logconst [k] expected, got ",
+                                    means.dim(), "-D, ", transforms.dim(), "-D and ", logconst.dim(), "-D"));
+    for (const at::Tensor* t : {&means, &transforms, &logconst}) {
+      if (t->scalar_type() != at::kDouble)
+        throw py::type_error(str_cat(what, ": means, transforms and logconst must be float64"));
+      if (t->is_cuda() && t->device() != x.device())
+        throw py::value_error(str_cat(what, ": means, transforms and logconst must be on x's device or on the host"));
+    }
+    GmmArgs a;
+    a.n = x.size(0), a.d = x.size(1), a.k = means.size(0);
+    if (a.n < 1) throw py::value_error(str_cat(what, ": at least one row expected"));
+    if (means.size(1) != a.d || transforms.size(0) != a.k || transforms.size(1) != a.d || transforms.size(2) != a.d ||
+        logconst.size(0) != a.k)
+      throw py::value_error(str_cat(what, ": x has cells of ", a.d, " components, means is [", a.k, ", ", means.size(1),
+                                    "], transforms [", transforms.size(0), ", ", transforms.size(1), ", ",
+                                    transforms.size(2), "] and logconst [", logconst.size(0), "]"));
+    if (a.d < 1 || a.d > k::kGmmMaxD || a.k < 1 || a.k > k::kGmmMaxK || a.k * a.d * a.d > k::kGmmMaxKDD)
+      throw py::value_error(str_cat(what, ": 1 <= d <= ", k::kGmmMaxD, ", 1 <= k <= ", k::kGmmMaxK, " and k d^2 <= ",
+                                    k::kGmmMaxKDD, " expected, got d = ", a.d, ", k = ", a.k));
+    a.means = means.to(x.device()).contiguous();
+    a.transforms = transforms.to(x.device()).contiguous();
+    a.logconst = logconst.to(x.device()).contiguous();
+    return a;
+  };
+  m.def("gmm_step", [gmm_args](const at::Tensor& x, const at::Tensor& means, const at::Tensor& transforms,
+                               const at::Tensor& logconst, const py::object& slice_rows) {
+    const char* what = "gmm_step";
+    const GmmArgs a = gmm_args(what, x, means, transforms, logconst);
+    int64_t forced = 0;
+    if (!slice_rows.is_none()) {
+      if (!py::isinstance<py::int_>(slice_rows) || py::isinstance<py::bool_>(slice_rows))
+        throw py::type_error(str_cat(what, ": slice_rows must be an int or None"));
+      forced = slice_rows.cast<int64_t>();
+      if (forced < 1 || forced % k::kGmmStage)
+        throw py::value_error(str_cat(what, ": slice_rows must be a positive multiple of ", k::kGmmStage, ", got ",
+                                      forced));
+    }
+    const int d = static_cast<int>(a.d), kk = static_cast<int>(a.k);
+    const k::GmmPlan plan = k::gmm_plan(a.n, d, kk, forced);
+    c10::hip::HIPGuard guard(x.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+    const auto f64 = x.options().dtype(at::kDouble);
+    at::Tensor N = pool_empty({a.k}, f64), S = pool_empty({a.k, a.d}, f64), C = pool_empty({a.k, a.d, a.d}, f64),
+               loglik = pool_empty({1}, f64), bad = pool_empty({1}, x.options().dtype(at::kLong));
+    at::Tensor ws = pool_empty({static_cast<int64_t>((plan.workspace_bytes + 7) / 8)}, f64);
+    k::gmm_step(x.data_ptr(), from_scalar_type(x.scalar_type()), a.n, d, kk, a.means.data_ptr<double>(),
+                a.transforms.data_ptr<double>(), a.logconst.data_ptr<double>(), plan, N.data_ptr<double>(),
+                S.data_ptr<double>(), C.data_ptr<double>(), loglik.data_ptr<double>(), bad.data_ptr<int64_t>(),
+                ws.data_ptr(), static_cast<size_t>(ws.numel()) * 8, s);
+    return py::make_tuple(N, S, C, loglik, bad);
+  }, py::arg("x"), py::arg("means"), py::arg("transforms"), py::arg("logconst"), py::arg("slice_rows") = py::none(),
+     "one EM step of a Gaussian mixture: x [n, d] (float32 or float64, contiguous, on the device, n >= 1), means [k, d], "
+     "transforms [k, d, d] (T_j = L_j^-1, lower triangular, Sigma_j = L_j L_j^T; what lies above the diagonal is taken "
+     "as zero) and logconst [k] (c_j = log w_j - (d / 2) log 2 pi - sum_i log L_j,ii), float64, on x's device or on the "
+     "host; 1 <= k <= 64, 1 <= d <= 128, k d^2 <= 262144 -> (N f64 [k], S f64 [k, d], C f64 [k, d, d], loglik f64 [1], bad "
+     "int64 [1]). log p_ij = c_j - ||T_j (x_i - mu_j)||^2 / 2 on the f64 MFMA (the mean is subtracted from the operand; a "
+     "stripe of 64 rows stays in LDS for all k components; no [n, k, d] array), r_ij = exp(log p_ij - lse_i); N = sum_i "
+     "r_ij, S = sum_i r_ij (x_i - mu_j), C = sum_i r_ij (x_i - mu_j)(x_i - mu_j)^T (k weighted SYRKs of [x - mu_j, 1] over row "
+     "slices folded in slice order; exactly symmetric), loglik = sum_i lse_i, bad the rows left out for a NaN or an "
+     "infinity. The same bits on every run. slice_rows (a multiple of 32) forces the rows per slice; None chooses it "
+     "from (n, d, k)");
+  m.def("gmm_predict", [gmm_args](const at::Tensor& x, const at::Tensor& means, const at::Tensor& transforms,
+                                  const at::Tensor& logconst) {
+    const GmmArgs a = gmm_args("gmm_predict", x, means, transforms, logconst);
+    c10::hip::HIPGuard guard(x.device().index());
+    hipStream_t s = c10::hip::getCurrentHIPStream(x.device().index()).stream();
+    at::Tensor prob = pool_empty({a.n, a.k}, x.options().dtype(at::kDouble)),
+               pred = pool_empty({a.n}, x.options().dtype(at::kInt));
+    k::gmm_predict(x.data_ptr(), from_scalar_type(x.scalar_type()), a.n, static_cast<int>(a.d), static_cast<int>(a.k),
+                   a.means.data_ptr<double>(), a.transforms.data_ptr<double>(), a.logconst.data_ptr<double>(),
+                   prob.data_ptr<double>(), pred.data_ptr<int32_t>(), s);
+    return py::make_tuple(prob, pred);
+  }, py::arg("x"), py::arg("means"), py::arg("transforms"), py::arg("logconst"),
+     "the E step of gmm_step alone: (prob f64 [n, k], pred int32 [n]); prob are the responsibilities r_ij, pred the first "
+     "largest of a row; zeros and -1 for a row that holds a NaN or an infinity");
   // the CSR of a grouped call: perm [n] and offsets [nseg + 1] on the columns' device; returns nseg
   auto group_csr = [group_index](const char* what, const at::Tensor& perm, const at::Tensor& offsets,
                                  const at::Device& dev, int64_t n) {

@@ -494,6 +494,50 @@ void logreg_step(const void* x, DType dtype, const void* y, DType ydtype, const 
                  double* grad, double* wsum, int64_t* bad, void* workspace, size_t workspace_size, hipStream_t s);
 void logreg_predict(const void* x, DType dtype, int64_t n, int d, int R, const double* coef, const double* icpt,
                     double logit_threshold, int32_t* pred, double* raw, double* prob, hipStream_t s);
+// ---- vector columns (gmm.hip): ml.clustering.GaussianMixture
+// One EM step over x [n][d], row-major f32 or f64, aligned to the element,
+// against means [k][d], transforms [k][d][d] (T_j = L_j^-1, lower triangular,
+// Sigma_j = L_j L_j^T) and logconst [k] (c_j = log w_j - (d / 2) log 2 pi - sum_i
+// log L_j,ii), all f64 on the device. n >= 1, 1 <= k <= kGmmMaxK, 1 <= d <=
+// kGmmMaxD, k d^2 <= kGmmMaxKDD, and the workspace (n k responsibilities, two
+// words a stripe of 64 rows, 4096 words per slice, component and tile pair)
+// stays under kGmmMaxWorkspace: n k < 2^28 less the partials (GraphError if
+// not).
+//   gmm_step     gm_estep (a stripe of 64 rows stays in LDS as f64 for all k
+//                components; z = T_j (x - mu_j) on the f64 MFMA, tiles above
+//                the diagonal skipped; log p_ij = c_j - ||z||^2 / 2 kept in LDS;
+//                a safe log-sum-exp row epilogue writes r [n][k] to the
+//                workspace; per block the sum of lse and the count of
+//                left-out rows), gm_mstep (G_j = sum_i r_ij [x - mu_j, 1][x -
+//                mu_j, 1]^T: k weighted SYRKs over (slice) x (component) x
+//                (upper tile pair); the ones column carries N and S) and
+//                gm_finish (folds in slice and block order, mirrors C): N [k],
+//                S [k][d] = sum r (x - mu_j), C [k][d][d] = sum r (x - mu_j)(x -
+//                mu_j)^T, loglik [1] = sum lse, bad [1] int64 = rows left out
+//                for a NaN or an infinity (r = 0, no lse).
+//   gmm_predict  gm_estep alone: prob [n][k] = r, pred [n] int32 = the first
+//                largest r_j; a left-out row gets zeros and -1.
+// No float atomics, no block waits for another one: the bits depend on (n, d,
+// k, slice_rows) alone.
+constexpr int kGmmMaxK = 64;
+constexpr int kGmmMaxD = 128;
+constexpr int kGmmMaxKDD = 262144;
+constexpr int kGmmStage = 32;  // rows per stage of gm_mstep: slice_rows is a multiple
+constexpr size_t kGmmMaxWorkspace = size_t(1) << 31;
+struct GmmPlan {
+  int tiles = 0, pairs = 0;        // gm_mstep: 64-wide tiles of the d + 1 entries, pairs bi <= bj
+  int64_t blocks = 0;              // gm_estep: stripes of 64 rows
+  int64_t slice_rows = 0, slices = 0;
+  size_t workspace_bytes = 0;
+};
+// slice_rows <= 0: chosen from (n, d, k) so that gm_mstep's grid fills the
+// device about twice; otherwise a multiple of 32
+GmmPlan gmm_plan(int64_t n, int d, int k, int64_t slice_rows);
+void gmm_step(const void* x, DType dtype, int64_t n, int d, int k, const double* means, const double* transforms,
+              const double* logconst, const GmmPlan& plan, double* N, double* S, double* C, double* loglik,
+              int64_t* bad, void* workspace, size_t workspace_size, hipStream_t s);
+void gmm_predict(const void* x, DType dtype, int64_t n, int d, int k, const double* means, const double* transforms,
+                 const double* logconst, double* prob, int32_t* pred, hipStream_t s);
 // hist[p][d] (device int64 [P][256], overwritten) = rows whose word has its top
 // prefix_bits bits (0, 8, ..., 56) equal to those of prefixes[p] (host) and whose
 // next 8-bit digit is d; prefix_bits == 0 takes P == 1 and ignores the prefix.
